@@ -2,7 +2,10 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 launched by
 ``torch.distributed.run`` (one rank per GPU, RCCL only for bench bookkeeping).  Rank 0 prints ONE
-JSON line.
+JSON line.  Such a plain run does only what the headline needs: set up, warm up, time the K steps,
+print the line.  ``--full`` adds every other measurement below to the line.  ``--dump-outputs DIR``
+writes what the last timed step returned (see dump_outputs) for output-for-output comparison of two
+builds; the inputs are seeded, so they are identical from run to run.
 
 Headline workload (BASELINE.json configs[1] = SURVEY §8(d) config 2): per GPU a 4096-molecule
 QM9-shaped batch (synthetic, seeded per rank -> weak scaling), hidden 300, depth 3, fp32, ReLU,
@@ -15,11 +18,12 @@ Other workloads (``--workload``): ``qm9-1m-sharded`` is BASELINE config 4: ONE s
 1,000,000-molecule batch cut into 8 edge-balanced contiguous shards (shard.edge_balanced_ranges);
 rank r of N runs shards r, r + N, ... each as its own collated batch (N = 8: one 125k shard per
 GPU; N = 1: all eight in turn) -> fixed total work ("strong").  ``zinc-4096-bf16`` is config 3,
-``polymer-16`` config 5; both are also measured in every default run as ``secondary`` keys.
+``polymer-16`` config 5; both are also measured in every ``--full`` run as ``secondary`` keys.
 
-Also in the line:
+Also in the line with ``--full``:
 * ``roofline`` for the dominant kernel (the fused layer update; per-launch duration from HIP events
-  recorded on the launch stream around every launch inside the timed region), with SURVEY §8(d)'s
+  recorded on the launch stream around every launch of a sampling pass that repeats the timed steps
+  right after the timed region), with SURVEY §8(d)'s
   definitions: ``frac`` = t_min / launch time, t_min = max(algorithmic bytes / 8 TB/s, the MFMA
   products the kernel issues / the peak of that MFMA type) -- the roof of the instructions it really
   runs (fp32 storage: 3 fp16 products per MAC at 2.5 PF, so HBM binds at h = 300); ``hbm_frac`` =
@@ -82,12 +86,17 @@ def parse():
                         "reaches its sustained clock only after ~1 s of load (measured: the layer "
                         "kernel runs 115 us right after a cold start, 106-109 us at steady state)")
     p.add_argument("--workload", default="qm9-4096", choices=sorted(WORKLOADS))
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: roofline, secondary workloads, fresh-batch / "
+                        "embedded / end-to-end legs, training and the CPU baseline (each can be switched off "
+                        "with its --no-* option)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32; a fixed seeded row "
+                        "sample where an array is large, at most 64 MB in all)")
     p.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline budget per thread count")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--event-every", type=int, default=8,
-                   help="the roofline's per-launch HIP events on every N-th step of the timed region (each "
-                        "event record costs the step about 7 us, so recording every step would slow the "
-                        "headline it sits in by about 5 %%)")
+                   help="the roofline's per-launch HIP events on every N-th step of its sampling pass (--full)")
     p.add_argument("--no-embedded", action="store_true", help="skip embedded / fresh / end-to-end legs")
     p.add_argument("--no-secondary", action="store_true", help="skip the config-3 / config-5 keys")
     p.add_argument("--no-training", action="store_true", help="skip the training key (N=1 only)")
@@ -418,32 +427,50 @@ def run_workload(name, args, env, dev, headline):
     torch.cuda.synchronize(dev)
 
     events = []
-    # at least two sampled steps, at most one in `event_every`, none at the region's edges
+    # at least two sampled steps, at most one in `event_every`, none at the pass's edges
     every = max(1, args.event_every, args.steps // 2)
     offset = max(0, min(every // 2, args.steps - 1))
     count = [0]
+    last = []  # (block output, readout output) per job of the last timed step, for --dump-outputs
+    keep_at = args.steps - 1 if headline and args.dump_outputs else -1
 
     def step():
-        # the per-launch roofline events ride on the steps i = offset mod every of the timed region;
-        # the others run exactly as a user's forward does
+        # exactly a user's forward; the last timed step's outputs stay alive for --dump-outputs
+        keep = count[0] == keep_at
+        count[0] += 1
+        for j in jobs:
+            if keep:
+                Gout = block(j.Gd)
+                last.append((Gout, readout(Gout)))
+            else:
+                readout(block(j.Gd))
+
+    def sampled_step():
+        # the roofline's sampling pass (--full): per-launch events on the steps i = offset mod every
         _engine.UPDATE_EVENTS = events if count[0] % every == offset else None
         count[0] += 1
         for j in jobs:
             readout(block(j.Gd))
 
+    count[0] = -(1 << 62)  # prewarm and warm-up steps never reach keep_at
     with torch.no_grad():
         prewarm(step, args.prewarm_s, dev)
         for _ in range(args.warmup):
             step()
-    events.clear()
     count[0] = 0
     elapsed = timed_steps(step, args.steps, 0, env, dev)
-    _engine.UPDATE_EVENTS = None
     info = dict(_engine.LAST_UPDATE_INFO)
+    if args.full:
+        count[0] = 0
+        with torch.no_grad():
+            for _ in range(args.steps):
+                sampled_step()
+        torch.cuda.synchronize(dev)
+        _engine.UPDATE_EVENTS = None
     E_rank = sum(j.E for j in jobs)
     units, secs, rate = aggregate_throughput(E_rank * depth * args.steps, elapsed, device=BOOK_DEV)
     res = {"jobs": jobs, "embedding": embedding, "block": block, "readout": readout, "events": events,
-           "event_every": every, "event_offset": offset,
+           "event_every": every, "event_offset": offset, "last": last,
            "info": info, "units": units, "secs": secs, "rate": rate, "batch": batch, "ranges": ranges,
            "name": name, "kind": kind, "h": h, "depth": depth, "bf16": bf16, "n_mols": n_mols,
            "steps": args.steps}
@@ -622,7 +649,8 @@ def summary(res, args, env, pmc_csv=None):
         traffic, tsrc = committed_traffic(res["name"], kern)
     roof = launch_roofline(jobs, res["events"], info, traffic, tsrc)
     roof["launch_sampling"] = (f"HIP events on the launch stream around every layer launch of the steps "
-                               f"i = {res['event_offset']} mod {res['event_every']} of the timed region "
+                               f"i = {res['event_offset']} mod {res['event_every']} of a pass of the same "
+                               f"{args.steps} steps right after the timed region "
                                f"({len(res['events'])} launches)")
     t_step = res["secs"] / args.steps
     V = sum(j.V for j in jobs)
@@ -642,6 +670,36 @@ def summary(res, args, env, pmc_csv=None):
         "binding_frac": t_min / t_step,
         "t_min_us": t_min * 1e6,
     }
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all arrays of a --dump-outputs directory together stay below 64 MB
+
+
+def dump_outputs(last, out_dir, env):
+    """--dump-outputs DIR: what the last timed step returned to its caller, per job the readout
+    (``readout``) and the block's output graph (``node_feats``, ``edge_feats``), as float32
+    DIR/<name>.npy; ``_shard<i>`` is appended where a rank runs several jobs and ``rank<r>_`` put in
+    front when several ranks run.  An array over its share of the budget is cut to a fixed, seeded
+    sample of its rows (sorted row numbers in DIR/<name>_rows.npy, float64), so two builds run with
+    the same arguments write the same rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{env.rank}_" if env.world_size > 1 else ""
+    per_job = DUMP_BUDGET_BYTES // max(1, len(last))
+    for i, (Gout, out) in enumerate(last):
+        suffix = f"_shard{i}" if len(last) > 1 else ""
+        for name, t, share in (("readout", out, 2), ("node_feats", Gout.node_feats, 4),
+                               ("edge_feats", Gout.edge_feats, 4)):
+            t = t.detach()
+            row_bytes = 4 * max(1, t.numel() // max(1, t.shape[0]))
+            rows_max = max(1, (per_job // share) // row_bytes)
+            if t.shape[0] > rows_max:
+                gen = torch.Generator().manual_seed(1234 + i)
+                rows = torch.randperm(t.shape[0], generator=gen)[:rows_max].sort().values
+                np.save(os.path.join(out_dir, f"{prefix}{name}{suffix}_rows.npy"), rows.double().numpy())
+                t = t[rows.to(t.device)]
+            np.save(os.path.join(out_dir, f"{prefix}{name}{suffix}.npy"), t.float().cpu().numpy())
 
 
 def launch_check(args, env):
@@ -685,8 +743,10 @@ def main():
     _lib.load()  # fail loudly if the HIP extension is missing
     res = run_workload(args.workload, args, env, dev, headline=True)
     job = res["jobs"][0]
-    fresh = embedded = e2e = None
-    if not args.no_embedded and res["kind"] != "qm9v":
+    if args.dump_outputs:
+        dump_outputs(res.pop("last"), args.dump_outputs, env)
+    fresh = embedded = e2e = roof = fwd = None
+    if args.full and not args.no_embedded and res["kind"] != "qm9v":
         fresh = fresh_batch_leg(res, args, env, dev)
         embedded = embedded_leg(res, args, env, dev)
         if env.rank == 0:
@@ -697,10 +757,11 @@ def main():
                 share = os.cpu_count() or 4
             share = min(int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or share, share, 16)
             e2e["pipelined"] = pipeline_leg(res, dev, workers=max(4, share - 2))
-    roof, fwd = summary(res, args, env, args.pmc_csv)
+    if args.full:
+        roof, fwd = summary(res, args, env, args.pmc_csv)
 
     secondary = None
-    if not args.no_secondary and args.workload == "qm9-4096":
+    if args.full and not args.no_secondary and args.workload == "qm9-4096":
         secondary = {}
         for name in SECONDARY:
             r2 = run_workload(name, args, env, dev, headline=False)
@@ -715,11 +776,11 @@ def main():
             del r2
 
     training = None
-    if not args.no_training and env.world_size == 1 and args.workload == "qm9-4096":
+    if args.full and not args.no_training and env.world_size == 1 and args.workload == "qm9-4096":
         training = training_leg(args)
 
     cpu = None
-    if not args.no_cpu_baseline and env.rank == 0:
+    if args.full and not args.no_cpu_baseline and env.rank == 0:
         cpu = cpu_baseline(job, res["embedding"], args.cpu_seconds)
     if env.rank == 0:
         sharded = res["kind"] == "qm9v"
