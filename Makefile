@@ -3,7 +3,7 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 SRC_DIR := notorch_amd/csrc
 SRCS    := $(wildcard $(SRC_DIR)/*.hip)
-HDRS    := $(wildcard $(SRC_DIR)/*.hpp) $(wildcard $(SRC_DIR)/diag/*.hpp) include/notorch_amd.h
+HDRS    := $(wildcard $(SRC_DIR)/*.hpp) $(wildcard $(SRC_DIR)/diag/*.hpp) include/notorch_amd.h include/notorch_amd_train.h
 FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result \
            -fvisibility=hidden -DNT_BUILD
 # DIAG=1: the diagnostic library (A/B kernel variants, ablation and stamp builds selected by NT_*

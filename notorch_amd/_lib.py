@@ -4,7 +4,8 @@ The library is the only compute path of this package: there is no CPU or eager-t
 the forward kernels.  If the shared object is missing, every op raises :class:`NativeLibraryError`
 (build it with ``python -c "import __graft_entry__ as g; g.build()"`` or ``make``).
 
-Signatures mirror ``include/notorch_amd.h`` one-to-one.
+Signatures mirror ``include/notorch_amd.h`` one-to-one (``SIGNATURES``); the training-side additions
+of ``include/notorch_amd_train.h`` are bound from ``EXT_SIGNATURES``.
 """
 from __future__ import annotations
 
@@ -152,6 +153,15 @@ SIGNATURES: dict[str, tuple] = {
     ),
 }
 
+# include/notorch_amd_train.h: additive entry points of the same library (ABI_VERSION unchanged)
+EXT_SIGNATURES: dict[str, tuple] = {
+    "nt_embed_bag_backward_workspace": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "nt_embed_bag_backward": (
+        _c_int,
+        [_vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_i64, _vp],
+    ),
+}
+
 
 class NativeLibraryError(RuntimeError):
     """The HIP extension is missing, stale or returned an error."""
@@ -181,6 +191,12 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in EXT_SIGNATURES.items():
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise NativeLibraryError(f"libnotorch_amd lacks {name} (include/notorch_amd_train.h); rebuild")
             fn.restype = res
             fn.argtypes = args
         ver = lib.nt_abi_version()

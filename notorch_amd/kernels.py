@@ -38,6 +38,7 @@ __all__ = [
     "embed_bag",
     "dmpnn_init_embed",
     "embed_edge_records",
+    "embed_bag_backward",
     "node_scores",
     "softmax_pool",
     "dense_matmul",
@@ -1125,6 +1126,66 @@ def embed_edge_records(node_types: Tensor, num_node_types: int, edge_types: Tens
     out = torch.empty(max(E, 1), 4, dtype=torch.int32, device=dev)[:E]
     _run(dev, _lib.load().nt_embed_edge_records, _ptr(node_types.contiguous()), int(num_node_types),
          _ptr(edge_types.contiguous()), int(num_edge_types), _ptr(src), _ptr(perm), V, E, _ptr(out), _stream(dev))
+    return out
+
+
+def embed_bag_backward(dX: Tensor, idx: Tensor, ntypes: int, seg_ptr: Tensor | None = None,
+                       perm: Tensor | None = None, pitch: int | None = None,
+                       out_dtype: torch.dtype | None = None) -> Tensor:
+    """Table gradient of a sum-mode EmbeddingBag (nt_embed_bag_backward): dT[t] = sum of R[i] over every
+    (i, j) with idx[i, j] == t, accumulated in fp32 and rounded once to out_dtype (default dX's).
+    R[i] = dX[i], or with the CSR (seg_ptr int32[n + 1], perm int32 over dX's rows, from csr_build)
+    R[i] = sum of dX[perm[p]] over segment i.  dX: fp32 or bf16 rows, contiguous or a row-padded view
+    (pitch: its row pitch in elements when it is not the tensor's own stride).  A type no index names
+    gets a zero row; indices outside [0, ntypes) contribute nothing (the forward validates them).
+    Deterministic: per-workgroup LDS partial tables combined in a fixed order, no float atomics; tables
+    past the LDS partial are taken in chunks of type rows by the same kernel."""
+    dev = _require_device(dX, idx, seg_ptr, perm)
+    if dX.dim() != 2:
+        raise ValueError("dX must be 2-D")
+    if dX.dtype not in _DTYPE_CODES:
+        raise TypeError(f"dX must be float32 or bfloat16, got {dX.dtype}")
+    n_dx, h = dX.shape
+    if pitch is None:
+        if dX.is_contiguous():
+            pitch = h
+        elif dX.stride(1) == 1 and dX.stride(0) >= h:
+            pitch = dX.stride(0)
+        else:
+            raise ValueError("dX must be contiguous or a row-padded view (unit column stride)")
+    pitch = int(pitch)
+    if pitch < h or (n_dx > 1 and dX.stride(0) != pitch) or (n_dx > 0 and h > 1 and dX.stride(1) != 1):
+        raise ValueError("pitch must be dX's row stride (>= h)")
+    _require_i64("idx", idx)
+    if idx.dim() != 2:
+        raise ValueError("idx must be n x k type indices")
+    n, k = idx.shape
+    if ntypes < 0 or h <= 0:
+        raise ValueError("ntypes must be >= 0 and h > 0")
+    if (seg_ptr is None) != (perm is None):
+        raise ValueError("the CSR needs both seg_ptr and perm")
+    if seg_ptr is None:
+        if n_dx != n:
+            raise ValueError("without a CSR dX needs one row per row of idx")
+    else:
+        if seg_ptr.dtype != torch.int32 or seg_ptr.numel() != n + 1 or not seg_ptr.is_contiguous():
+            raise ValueError("seg_ptr must be contiguous int32 of length n + 1")
+        if perm.dtype != torch.int32 or perm.numel() != n_dx or not perm.is_contiguous():
+            raise ValueError("perm must be contiguous int32 with one entry per row of dX")
+    out_dtype = dX.dtype if out_dtype is None else out_dtype
+    if out_dtype not in _DTYPE_CODES:
+        raise TypeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
+    out = torch.empty(ntypes, h, dtype=out_dtype, device=dev)
+    if ntypes == 0:
+        return out
+    lib = _lib.load()
+    ws_bytes = lib.nt_embed_bag_backward_workspace(n, ntypes, h)
+    if ws_bytes < 0:
+        raise ValueError("bad sizes for embed_bag_backward")
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    _run(dev, lib.nt_embed_bag_backward,
+         _ptr(dX), pitch, n_dx, _ptr(idx), n, k, int(ntypes), h, _ptr(seg_ptr), _ptr(perm),
+         _DTYPE_CODES[dX.dtype], _DTYPE_CODES[out_dtype], _ptr(out), _ptr(ws), ws_bytes, _stream(dev))
     return out
 
 

@@ -1042,6 +1042,133 @@ class ChempropBlockFunction(torch.autograd.Function):
         return (*res_inputs, None, None, None, None, None, None, None, None, None, *res_params)
 
 
+def _grad_rows(g: Tensor) -> Tensor:
+    """A gradient as rows nt_embed_bag_backward reads: contiguous, or a row-padded view."""
+    if g.is_contiguous() or (g.dim() == 2 and g.stride(1) == 1 and g.stride(0) >= g.shape[1]):
+        return g
+    return g.contiguous()
+
+
+class EmbedBagFunction(torch.autograd.Function):
+    """One sum-mode EmbeddingBag on the kernels: nt_embed_bag forward, nt_embed_bag_backward (the
+    deterministic LDS reduction, no CSR) for the table gradient."""
+
+    @staticmethod
+    def forward(ctx, table, idx, validate):
+        ctx.save_for_backward(idx)
+        ctx.table = (table.shape[0], table.dtype)
+        ctx.set_materialize_grads(False)
+        return K.embed_bag(table.detach(), idx, validate=validate)
+
+    @staticmethod
+    def backward(ctx, dX):
+        if dX is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        (idx,) = ctx.saved_tensors
+        ntypes, dtype = ctx.table
+        return K.embed_bag_backward(_grad_rows(dX), idx, ntypes, out_dtype=dtype), None, None
+
+
+class EmbeddedBlockFunction(torch.autograd.Function):
+    """The embedded encoder (GraphEmbedding fused into the block's initial gather) under autograd.
+    Forward: block_forward_embedded's kernels with the layer states kept.  Backward: block_backward
+    down to G = dL/dH0 (dXv is never reduced), then nt_embed_bag_backward twice over G: the edge table
+    from (G, edge_types), the node table from (G, node_types) through the src CSR.  A table or parameter
+    that needs no gradient gets None and no launch.  NT_BWD=torch: the recompute-in-torch backward of
+    the unfused pair (A/B reference only)."""
+
+    NFIX = 14  # inputs ahead of the layer parameters
+
+    @staticmethod
+    def forward(ctx, node_table, edge_table, node_types, edge_types, edge_index, rev, lay, act_mod, act, reduce,
+                residual, nlayers, drop, validate, *params):
+        weights = list(params[:nlayers])
+        biases = list(params[nlayers:])
+        src = edge_index[0].contiguous()
+        V = node_types.shape[0]
+        kernel_bwd = os.environ.get("NT_BWD", "kernel") != "torch"
+        Tv, Te = node_table.detach(), edge_table.detach()
+        if nlayers == 0:
+            H, _ = K.dmpnn_init_embed(Tv, node_types, Te, edge_types, src, validate=validate)
+            node, H, states = _layers_forward(H, None, V, src, rev, lay, weights, biases, act, reduce, residual,
+                                              kernel_bwd, drop)
+        else:
+            amax = _amax_buffer(nlayers, Tv)
+            k72 = node_types.shape[1] == 7 and edge_types.shape[1] == 2
+            rec = None
+            if k72 and Tv.dtype == torch.float32 and embed_wave_ok(Tv.shape[0], Te.shape[0], Tv.shape[1]):
+                rec = embed_records(lay, node_types, Tv.shape[0], edge_types, Te.shape[0], src)
+            H, S = K.dmpnn_init_embed(Tv, node_types, Te, edge_types, src, lay.dst_ptr, lay.dst_perm, act=act,
+                                      reduce=reduce, validate=validate, amax=None if amax is None else amax[0],
+                                      records=rec)
+            node, H, states = _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual,
+                                              kernel_bwd, drop, amax)
+        flat = [t for hs in states for t in hs]
+        if kernel_bwd and reduce in ("max", "min"):
+            flat.append(H)  # the final node scatter's arg is taken over H_d
+        ctx.save_for_backward(node_table, edge_table, node_types, edge_types, edge_index, rev,
+                              *[p if p is not None else torch.empty(0) for p in params], *flat)
+        ctx.cfg = (act_mod, act, reduce, residual, nlayers, [p is None for p in params], lay, kernel_bwd, drop)
+        ctx.set_materialize_grads(False)  # an unused output arrives as None (see ChempropBlockFunction)
+        return node, H
+
+    @staticmethod
+    def backward(ctx, dnode, dH):
+        act_mod, act, reduce, residual, nlayers, is_none, lay, kernel_bwd, drop = ctx.cfg
+        node_table, edge_table, node_types, edge_types, edge_index, rev, *rest = ctx.saved_tensors
+        nfix = EmbeddedBlockFunction.NFIX
+        nparams = len(is_none)
+        params = [None if n else p for p, n in zip(rest[:nparams], is_none)]
+        need = ctx.needs_input_grad
+        if dnode is None and dH is None:
+            return (None,) * (nfix + nparams)
+        V, E = node_types.shape[0], edge_types.shape[0]
+        if kernel_bwd:
+            flat = rest[nparams:]
+            states = [tuple(flat[3 * i:3 * i + 3]) for i in range(nlayers)]
+            H_last = flat[3 * nlayers] if reduce in ("max", "min") else None
+            src = edge_index[0].contiguous()
+            dst = edge_index[1].contiguous()
+            _, G, dWs, dbs = block_backward(dnode, dH, states, params[:nlayers], src, dst, rev, lay, act, reduce,
+                                            residual, V, (False, need[0] or need[1]), drop, H_last)
+            dTv = dTe = None
+            if need[1]:
+                dTe = K.embed_bag_backward(_grad_rows(G), edge_types, edge_table.shape[0],
+                                           out_dtype=edge_table.dtype)
+            if need[0]:  # R[v] = sum of G over v's out-edges (dXv), formed inside the reduction
+                src_ptr, src_perm = backward_layout(lay, src, rev, V, E)[:2]
+                dTv = K.embed_bag_backward(_grad_rows(G), node_types, node_table.shape[0], src_ptr, src_perm,
+                                           out_dtype=node_table.dtype)
+            res_params = [dW if need[nfix + i] else None for i, dW in enumerate(dWs)]
+            res_params += [None if p is None or not need[nfix + nlayers + i] else dbs[i]
+                           for i, p in enumerate(params[nlayers:])]
+            return (dTv, dTe, *([None] * (nfix - 2)), *res_params)
+        with torch.enable_grad():
+            tv = node_table.detach().requires_grad_(need[0])
+            te = edge_table.detach().requires_grad_(need[1])
+            Xv_ = torch.nn.functional.embedding_bag(node_types, tv, mode="sum")
+            Xe_ = torch.nn.functional.embedding_bag(edge_types, te, mode="sum")
+            ps = [None if p is None else p.detach().requires_grad_(True) for p in params]
+            masks = None
+            if drop is not None:
+                ones = torch.ones(E, edge_table.shape[1], dtype=edge_table.dtype, device=edge_table.device)
+                masks = [K.dropout_residual(ones, drop[0], drop[1], dropout_offset(l, E, ones.shape[1]))
+                         for l in range(nlayers)]
+            node, H = _torch_block(Xv_, Xe_, edge_index, rev, ps[:nlayers], ps[nlayers:], act_mod, reduce,
+                                   residual, masks)
+            leaves = [t for t in [tv, te] + ps if t is not None and t.requires_grad]
+            outs, grads = [], []
+            for o, g in ((node, dnode), (H, dH)):
+                if g is not None:
+                    outs.append(o)
+                    grads.append(g)
+            got = torch.autograd.grad(outs, leaves, grads, allow_unused=True)
+        it = iter(got)
+        res_tables = [next(it) if need[0] else None, next(it) if need[1] else None]
+        res_params = [None if p is None else next(it) for p in ps]
+        return (*res_tables, *([None] * (nfix - 2)), *res_params)
+
+
 def mol_chunks(G, mol_ptr: Tensor):
     """Chunk plan of the molecule CSR when some molecule has more than LONG_SEGMENT atoms (polymers,
     config 5), else None; cached on the layout with the molecule CSR it belongs to."""

@@ -7,9 +7,14 @@ optimizer sees new weights, so the forward re-packs them (one pack per layer wei
 Modes: `kernel` (the kernel backward, the weight grad per NT_WGRAD) and `torch` (the
 recompute-in-torch backward, NT_BWD=torch).  bench.py's `training` key runs this in fresh processes
 with --json (the default weight-grad path as the headline, NT_WGRAD=library as a comparison).
+--embedded trains the model users train, EmbeddedChempropBlock (GraphEmbedding fused into the block) + Sum,
+from the collated integer type indices: both embedding tables are in the optimizer and there are no
+Xv / Xe leaves.  --embed-bwd kernel (default) is the kernel path (EmbeddedBlockFunction: fused init,
+nt_embed_bag_backward for the tables); --embed-bwd torch is the library path that preceded it
+(block(embedding(G)) with nn.EmbeddingBag under autograd, NT_EMBED_BWD=torch).
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
-                                  [--optim adam|none] [--json]"""
+                                  [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--json]"""
 import argparse
 import json
 import os
@@ -21,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from notorch_amd.data.synth import make_batch  # noqa: E402
-from notorch_amd.nn import ChempropBlock, Sum  # noqa: E402
+from notorch_amd.nn import ChempropBlock, EmbeddedChempropBlock, GraphEmbedding, Sum  # noqa: E402
 
 
 def main():
@@ -42,6 +47,11 @@ def main():
                    help="adam: Adam(lr=1e-4).step() in every training step (the reference's default "
                         "optim_factory; torch's foreach implementation); adam-fused: the same optimizer "
                         "with torch's fused=True implementation; none: forward + backward only")
+    p.add_argument("--embedded", action="store_true",
+                   help="train EmbeddedChempropBlock + Sum from the type indices (the tables train; no Xv / Xe leaves)")
+    p.add_argument("--embed-bwd", default="kernel", choices=["kernel", "torch"],
+                   help="with --embedded: kernel = the fused kernel path; torch = block(embedding(G)) with "
+                        "nn.EmbeddingBag under autograd (NT_EMBED_BWD=torch)")
     p.add_argument("--json", action="store_true", help="print one JSON object instead of the table")
     a = p.parse_args()
     from notorch_amd import _lib
@@ -50,24 +60,33 @@ def main():
     dt = {"f32": torch.float32, "bf16": torch.bfloat16}[a.dtype]
     G = make_batch(a.kind, a.mols, seed=a.seed).collate("nodes")
     torch.manual_seed(0)
-    ev = torch.nn.EmbeddingBag(42, a.h, mode="sum")
-    ee = torch.nn.EmbeddingBag(13, a.h, mode="sum")
-    with torch.no_grad():
-        Xv, Xe = ev(G.node_feats).to(dt), ee(G.edge_feats).to(dt)
-    Gd = G.update(node_feats=Xv, edge_feats=Xe).to("cuda")
-    blk = ChempropBlock(a.h, depth=a.depth).to("cuda", dt).train()
     ro = Sum()
-    Xv_d = Gd.node_feats.requires_grad_(True)
-    Xe_d = Gd.edge_feats.requires_grad_(True)
     E = G.num_edges
+    if a.embedded:
+        os.environ["NT_EMBED_BWD"] = a.embed_bwd
+        Gd = G.to("cuda")  # node_feats / edge_feats stay the integer type columns
+        blk = EmbeddedChempropBlock(GraphEmbedding(42, 13, a.h), ChempropBlock(a.h, depth=a.depth))
+        blk = blk.to("cuda", dt).train()
+    else:
+        ev = torch.nn.EmbeddingBag(42, a.h, mode="sum")
+        ee = torch.nn.EmbeddingBag(13, a.h, mode="sum")
+        with torch.no_grad():
+            Xv, Xe = ev(G.node_feats).to(dt), ee(G.edge_feats).to(dt)
+        Gd = G.update(node_feats=Xv, edge_feats=Xe).to("cuda")
+        blk = ChempropBlock(a.h, depth=a.depth).to("cuda", dt).train()
+        Xv_d = Gd.node_feats.requires_grad_(True)
+        Xe_d = Gd.edge_feats.requires_grad_(True)
     opt = None
     if a.optim != "none":
         opt = torch.optim.Adam(blk.parameters(), lr=1e-4, **({"fused": True} if a.optim == "adam-fused" else {}))
 
     def step():
         blk.zero_grad(set_to_none=True)
-        Xv_d.grad = Xe_d.grad = None
-        out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
+        if a.embedded:
+            out = blk(Gd)
+        else:
+            Xv_d.grad = Xe_d.grad = None
+            out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
         ro(out).float().pow(2).sum().backward()
         if opt is not None:
             opt.step()
@@ -105,11 +124,13 @@ def main():
         print(json.dumps({
             "V": G.num_nodes, "E": E, "h": a.h, "depth": a.depth, "dtype": a.dtype,
             "weight_grad": os.environ.get("NT_WGRAD", "default"), "optim": a.optim,
+            **({"embedded": True, "embed_bwd": a.embed_bwd} if a.embedded else {}),
             "warmup": a.warmup, "steps": a.steps,
             "ms": res, "edge_messages_per_s": {k: E * a.depth / (v * 1e-3) for k, v in res.items()},
         }), flush=True)
         return
-    print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}")
+    print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}"
+          + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else ""))
     for k, v in res.items():
         print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s")
 
