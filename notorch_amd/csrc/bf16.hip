@@ -19,6 +19,8 @@
 //      whole 16-B row pieces with + bias + residual, rounded to bf16 once.
 // Two workgroups per CU (66.5 KiB LDS each) overlap one tile's gather with the other's MFMAs.
 // HBM bytes per edge: 4 rows x 2h (read H, gather S[src], gather H[rev], write H') + 16 B indices.
+// h > 512 (h % 8 == 0, <= 8192): update_bf16_wide_kernel walks the same tile in column passes and
+// K chunks of 512 (see there).
 #include "bf16.hpp"
 
 namespace nt {
@@ -518,6 +520,271 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
   }  // tile loop
 }
 
+// ------------------------------------------------------------------------------ update, h > 512
+// The same tile, wave split, fragment layout and epilogue as update_bf16_kernel<ACT, 8, 8, AGG>, in
+// a kernel of its own so that the h <= 512 instantiations keep their code.  A wave still owns eight
+// column tiles (128 accumulator VGPRs) and the A tile still holds 16 k steps (66.5 KB of LDS, two
+// workgroups per CU), so a tile is walked as
+//   for each column pass of <= 512 output columns:        acc = 0
+//     for each K chunk of <= 16 k steps (512 input columns):
+//       barrier, gather the chunk of A into the LDS tile, barrier, the chunk's MFMAs
+//     epilogue of the pass's columns (two 256-column staging rounds)
+// A is gathered once per column pass (ceil(h / 512) times per tile; the repeats hit L2), the B
+// fragments stream from Wp[global k step][column tile] one k step ahead across chunk boundaries, and
+// the index pipeline runs once per tile.  The MFMA order per output element is k ascending whatever
+// AGG is, so the fused H' equals the plain kernel's bit for bit.
+constexpr int kKSc = 16;                      // k steps per chunk
+constexpr int kLdaW = a_row_bytes(kKSc);      // 1040 B
+constexpr int kLdsW = kM * kLdaW > kStageB ? kM * kLdaW : kStageB;  // 66,560 B
+constexpr int kNTp = 4 * kNWMax;              // column tiles per pass (32 = 512 columns)
+
+template <int ACT, int AGG>
+__global__ void __launch_bounds__(kThreads, 2) update_bf16_wide_kernel(
+    const bf16_t* __restrict__ H, const bf16_t* __restrict__ S, const int64_t* __restrict__ src,
+    const int64_t* __restrict__ rev, const uint4* __restrict__ Wp, const bf16_t* __restrict__ bias,
+    int64_t V, int64_t E, int h, int KS, int NTn, int residual, int act, float alpha,
+    bf16_t* __restrict__ out, BfAgg agg, int ntiles, int nxcd) {
+  constexpr int NW = kNWMax;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ int64_t soff[kM], qoff[kM], erow[kM];
+  __shared__ int nstart[kM + 1], nnode[kM], nseg;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int G = gridDim.x;
+  const int64_t kstride = (int64_t)NTn * 64;
+  const int npass = (NTn + kNTp - 1) / kNTp, nchunk = (KS + kKSc - 1) / kKSc;
+
+  // index pipeline of the next tile, as update_bf16_kernel (once per tile, not per pass)
+  int cT = 0, cn = 0;
+  int ce = -1;
+  int cnode = -1, cprev = -2;
+  int cs = -1, cq = -1;
+  auto stage_a = [&](int t) {
+    if constexpr (AGG != 0) {
+      cT = agg.tile_ptr[t];
+      cn = agg.tile_ptr[t + 1] - cT;
+    } else {
+      cT = t * kM;
+      cn = E - (int64_t)cT < kM ? (int)(E - cT) : kM;
+    }
+  };
+  auto stage_b = [&]() {
+    ce = -1;
+    cnode = -1;
+    cprev = -2;
+    if (lane < cn) {
+      if constexpr (AGG != 0) {
+        ce = agg.perm[cT + lane];
+        cnode = agg.dsts[cT + lane];
+        cprev = lane > 0 ? agg.dsts[cT + lane - 1] : -2;
+      } else {
+        ce = cT + lane;
+      }
+    }
+  };
+  auto stage_c = [&]() {
+    const int64_t s = ce >= 0 ? (src ? src[ce] : (int64_t)ce) : -1, q = (ce >= 0 && rev) ? rev[ce] : -1;
+    cs = (s >= 0 && s < V) ? (int)s : -1;
+    cq = (q >= 0 && q < E) ? (int)q : -1;
+  };
+  int t_first = blockIdx.x, t_step = G, t_end = ntiles;
+  if (nxcd > 1 && G % nxcd == 0) {
+    const int x = (int)blockIdx.x % nxcd, chunk = (ntiles + nxcd - 1) / nxcd;
+    t_first = x * chunk + (int)blockIdx.x / nxcd;
+    t_step = G / nxcd;
+    t_end = min(ntiles, x * chunk + chunk);
+  }
+  if (w == 0 && t_first < t_end) {
+    stage_a(t_first);
+    stage_b();
+    stage_c();
+  }
+
+  for (int t = t_first; t < t_end; t += t_step) {
+    const bool has_next = t + t_step < t_end;
+    if (w == 0) {  // publish this tile's indices (the previous tile's epilogue ended with a barrier)
+      erow[lane] = ce;
+      soff[lane] = cs >= 0 ? (int64_t)cs * h : -1;
+      qoff[lane] = cq >= 0 ? (int64_t)cq * h : -1;
+      if constexpr (AGG != 0) {
+        const bool first = lane < cn && cnode != cprev;
+        const unsigned long long m = __ballot(first);
+        const int k = __popcll(m & ((1ull << lane) - 1ull));
+        if (first) {
+          nstart[k] = lane;
+          nnode[k] = cnode;
+        }
+        if (lane == 0) {
+          nseg = __popcll(m);
+          nstart[__popcll(m)] = cn;
+        }
+      }
+      if (has_next) stage_a(t + t_step);
+    }
+
+    for (int pass = 0; pass < npass; ++pass) {
+      // Column tile j of this wave in this pass is nt = 32 pass + w + 4 j.  Tiles past NTn (last
+      // pass only) load a clamped fragment and are never stored: no branch in front of a load.
+      const int nt0 = kNTp * pass + w;
+      auto boff = [&](int j) { return (nt0 + 4 * j < NTn ? nt0 + 4 * j : NTn - 1) * 64 + lane; };
+      // B fragments of the pass's first k step, in flight during the first gather
+      uint4 bcur[NW];
+#pragma unroll
+      for (int j = 0; j < NW; ++j) bcur[j] = Wp[boff(j)];
+      f32x4 acc[4][NW];
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int j = 0; j < NW; ++j) acc[mt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+      for (int kc = 0; kc < nchunk; ++kc) {
+        const int ks0 = kKSc * kc;
+        const int ksn = KS - ks0 < kKSc ? KS - ks0 : kKSc;
+        // the indices are published (first chunk) / every wave is done with the previous chunk or
+        // the previous pass's staging tile
+        __syncthreads();
+        // ---- 1. gather this chunk of A = S[src] - act(H[rev]) -> bf16 LDS tile [64][<= 512] ----
+        {
+          const int chunks = ksn * 4;  // 16-B pieces per row in this chunk
+          // rows in flight per round: 4, not the narrow kernel's 8, because the accumulators are
+          // live across this gather from the second chunk on (8 rows: 260-450 B of scratch per lane)
+          constexpr int kRG = 4;
+          for (int idx = lane; idx < chunks * (16 / kRG); idx += 64) {
+            const int c = idx % chunks, r0 = 16 * w + kRG * (idx / chunks);
+            const int k0 = 32 * ks0 + c * 8;
+            const int kcl = k0 < h ? k0 : h - 8;  // clamped, unconditional loads
+            uint4 sraw[kRG], qraw[kRG];
+#pragma unroll
+            for (int u = 0; u < kRG; ++u) {
+              const int64_t so = soff[r0 + u], qo = qoff[r0 + u];
+              sraw[u] = *reinterpret_cast<const uint4*>(S + (so >= 0 ? so : 0) + kcl);
+              qraw[u] = *reinterpret_cast<const uint4*>(H + (qo >= 0 ? qo : 0) + kcl);
+            }
+#pragma unroll
+            for (int u = 0; u < kRG; ++u) {
+              const int r = r0 + u;
+              const bool sok = soff[r] >= 0 && k0 < h, qok = qoff[r] >= 0 && k0 < h;
+              const unsigned su[4] = {sraw[u].x, sraw[u].y, sraw[u].z, sraw[u].w};
+              const unsigned qu[4] = {qraw[u].x, qraw[u].y, qraw[u].z, qraw[u].w};
+              bf16x8 a;
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const unsigned sb = (i & 1) ? (su[i >> 1] & 0xffff0000u) : (su[i >> 1] << 16);
+                const unsigned qb = (i & 1) ? (qu[i >> 1] & 0xffff0000u) : (qu[i >> 1] << 16);
+                const float sv = sok ? __uint_as_float(sb) : 0.f;
+                const float qv = qok ? __uint_as_float(qb) : 0.f;
+                a[i] = (__bf16)(sv - act_t<ACT>(qv, act, alpha));
+              }
+              *reinterpret_cast<uint4*>(lds + r * kLdaW + c * 16) = __builtin_bit_cast(uint4, a);
+            }
+          }
+        }
+        __syncthreads();
+        if (w == 0 && has_next && pass == 0 && kc == 0) stage_b();
+
+        // ---- 2. the chunk's MFMAs: acc[mt][j] += rows 16 mt.., columns of tile nt0 + 4 j ----
+        const char* arow = lds + (lane & 15) * kLdaW + 16 * (lane >> 4);
+        for (int ks = 0; ks < ksn; ++ks) {
+          // next global k step's fragments (the last one re-reads its own: no branch, no drain)
+          const int kg = ks0 + ks;
+          const int64_t kn = (kg + 1 < KS ? kg + 1 : kg) * kstride;
+          uint4 bnext[NW];
+#pragma unroll
+          for (int j = 0; j < NW; ++j) bnext[j] = Wp[kn + boff(j)];
+          bf16x8 a[4];
+#pragma unroll
+          for (int mt = 0; mt < 4; ++mt)
+            a[mt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(arow + 16 * mt * kLdaW + 64 * ks));
+#pragma unroll
+          for (int j = 0; j < NW; ++j) {
+            const bf16x8 b = __builtin_bit_cast(bf16x8, bcur[j]);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+              acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b, acc[mt][j], 0, 0, 0);
+          }
+#pragma unroll
+          for (int j = 0; j < NW; ++j) bcur[j] = bnext[j];
+        }
+        if (w == 0 && has_next && pass == 0 && kc == nchunk - 1) stage_c();
+      }
+      __syncthreads();  // every wave is done with the A tile: its LDS becomes the staging tile
+
+      // ---- 3. epilogue of this pass: 256 columns per round through LDS, + bias + residual ----
+      float* stage = reinterpret_cast<float*>(lds);
+      // p and jj fully unrolled: acc[][j] must only ever be indexed by constants
+#pragma unroll
+      for (int p = 0; p < NW / 4; ++p) {
+        const int n0 = 16 * kNTp * pass + 256 * p;
+        if (n0 >= h) break;
+        const int ncols = h - n0 < 256 ? h - n0 : 256;
+        // thread (tid) owns column piece c = 8 (tid & 31) of rows (tid >> 5) + 8 it, it < 8; its
+        // residual pieces are loaded before the staging round trip so their latency overlaps it
+        constexpr int kIt = kM * 32 / kThreads;
+        const int cpiece = 8 * (tid & 31);
+        const bool cok = cpiece < ncols;
+        auto load_res = [&](int it) {
+          const int64_t e = erow[(tid >> 5) + 8 * it];
+          const bool ok = cok && e >= 0 && residual;
+          return *reinterpret_cast<const uint4*>(H + (ok ? e * h + n0 + cpiece : 0));
+        };
+        uint4 hres[kIt];
+#pragma unroll
+        for (int it = 0; it < kIt; ++it) hres[it] = load_res(it);
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int j = 4 * p + jj;
+          if (nt0 + 4 * j < NTn) {
+            const int sc = 16 * w + 64 * jj + (lane & 15);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) stage[(16 * mt + 4 * (lane >> 4) + r) * kSO + sc] = acc[mt][j][r];
+          }
+        }
+        __syncthreads();
+        float bb[8];
+        if (bias && cok) load_chunk<8>(bias + n0 + cpiece, bb);
+        else for (int q = 0; q < 8; ++q) bb[q] = 0.f;
+#pragma unroll
+        for (int it = 0; it < kIt; ++it) {
+          const int r = (tid >> 5) + 8 * it;
+          const int64_t e = erow[r];
+          if (cok && e >= 0) {
+            float* st = stage + r * kSO + cpiece;
+            const uint4 hr = hres[it];
+            const unsigned hu[4] = {hr.x, hr.y, hr.z, hr.w};
+            float y[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              const unsigned hb = (q & 1) ? (hu[q >> 1] & 0xffff0000u) : (hu[q >> 1] << 16);
+              y[q] = st[q] + bb[q] + (residual ? __uint_as_float(hb) : 0.f);
+            }
+            store_chunk<8>(out + e * h + n0 + cpiece, y);
+            if constexpr (AGG != 0) {  // the aggregation reads the stored (bf16) value, as unfused
+#pragma unroll
+              for (int q = 0; q < 8; ++q) st[q] = AGG == 2 ? act_t<ACT>(rbf(y[q]), act, alpha) : rbf(y[q]);
+            }
+          }
+        }
+        if constexpr (AGG != 0) {
+          __syncthreads();
+          for (int k = tid >> 5; k < nseg; k += kThreads / 32) {
+            if (!cok) continue;
+            float y[8];
+            switch (agg.reduce) {
+              case NT_SUM: reduce_rows<NT_SUM>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
+              case NT_MEAN: reduce_rows<NT_MEAN>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
+              case NT_MAX: reduce_rows<NT_MAX>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
+              default: reduce_rows<NT_MIN>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
+            }
+            store_chunk<8>(agg.S_out + (int64_t)nnode[k] * h + n0 + cpiece, y);
+          }
+        }
+        __syncthreads();
+      }
+    }  // column passes
+  }  // tile loop
+}
+
 static bool valid_reduce(int r) { return r >= NT_SUM && r <= NT_MIN; }
 
 #define NT_BF_DISPATCH_A(ACT, LAUNCH)                                            \
@@ -648,15 +915,43 @@ static int launch_upd_nw(const void* H, const void* S, const int64_t* src, const
   return NT_EUNSUPPORTED;
 }
 
+// h > 512: the column-pass / K-chunk kernel (whole 16-B pieces only)
+template <int ACT, int AGG>
+static int launch_upd_wide(const void* H, const void* S, const int64_t* src, const int64_t* rev,
+                           const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
+                           int act, float alpha, void* H_out, int64_t grid, const BfAgg& agg,
+                           hipStream_t stream) {
+  const int KS = (int)((h + 31) / 32), NTn = (int)((h + 15) / 16);
+  auto kern = update_bf16_wide_kernel<ACT, AGG>;
+  NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsW));
+  const int64_t slots = 2 * (int64_t)cu_count();
+  const int64_t g = grid < slots ? grid : slots;
+  set_last_kernel("update_bf16_kernel: wide (h > 512), column passes x K chunks of 512, 64-edge tiles");
+  kern<<<(unsigned)g, kThreads, kLdsW, stream>>>(
+      (const bf16_t*)H, (const bf16_t*)S, src, rev, (const uint4*)Wp, (const bf16_t*)b, V, E, (int)h,
+      KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count());
+  NT_LAUNCH_CHECK();
+  return NT_OK;
+}
+
+bool bf16_update_supported(int64_t h) {
+  return h >= 1 && (h <= 4 * kNWMax * 16 || (h % 8 == 0 && h <= 8192));
+}
+
 int launch_update_bf16(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                        const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
                        int act, float alpha, void* H_out, hipStream_t stream) {
-  NT_REQUIRE(h <= 4 * kNWMax * 16, NT_EUNSUPPORTED, "bf16 update supports h <= 512");
+  NT_REQUIRE(bf16_update_supported(h), NT_EUNSUPPORTED, NT_BF16_H_RULE);
   const int64_t grid = (E + kM - 1) / kM;
   NT_REQUIRE(grid < (int64_t(1) << 31), NT_EINVAL, "too many edges");
   const bool vec = h % 8 == 0 && aligned16(H) && aligned16(S) && aligned16(H_out) &&
                    (b == nullptr || aligned16(b));
   const BfAgg none{nullptr, nullptr, nullptr, 0, 0, 0.f, nullptr};
+  if (h > 4 * kNWMax * 16) {
+    NT_REQUIRE(vec, NT_EINVAL, "bf16 with h > 512 needs 16-byte aligned feature pointers");
+    NT_BF_DISPATCH_A(act, return (launch_upd_wide<A_, 0>(H, S, src, rev, Wp, b, V, E, h, residual, act,
+                                                         alpha, H_out, grid, none, stream)));
+  }
   if (vec)
     NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 8, 0>(H, S, src, rev, Wp, b, V, E, h, residual,
                                                               act, alpha, H_out, grid, none, stream)));
@@ -666,7 +961,7 @@ int launch_update_bf16(const void* H, const void* S, const int64_t* src, const i
   return NT_OK;
 }
 
-bool bf16_fused_supported(int64_t h) { return h % 8 == 0 && h <= 4 * kNWMax * 16; }
+bool bf16_fused_supported(int64_t h) { return h % 8 == 0 && h >= 8 && h <= 8192; }
 
 int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                              const void* Wp, const void* b, int64_t V, int64_t E, int64_t h,
@@ -675,7 +970,7 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
                              int aact, float aalpha, void* H_out, void* S_out, hipStream_t stream) {
   if (tile_ptr == nullptr)  // no plan: the plain (unfused) kernel computes H_out only
     return launch_update_bf16(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha, H_out, stream);
-  NT_REQUIRE(bf16_fused_supported(h), NT_EUNSUPPORTED, "bf16 update_fused needs h % 8 == 0, h <= 512");
+  NT_REQUIRE(bf16_fused_supported(h), NT_EUNSUPPORTED, "bf16 update_fused needs h % 8 == 0, h <= 8192");
   NT_REQUIRE(perm && dsts && S_out && aligned16(S_out), NT_EINVAL, "fused aggregation needs perm, "
              "dst_sorted and a 16-byte aligned S_out");
   NT_REQUIRE(ntiles > 0 && ntiles < (int64_t(1) << 31), NT_EINVAL, "bad ntiles");
@@ -684,6 +979,16 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
   NT_REQUIRE(aact == NT_ACT_IDENTITY || (aact == act && aalpha == alpha), NT_EUNSUPPORTED,
              "bf16 update_fused: agg_act must be identity or equal to act");
   const BfAgg agg{tile_ptr, perm, dsts, reduce, aact, aalpha, (bf16_t*)S_out};
+  if (h > 4 * kNWMax * 16) {
+    NT_REQUIRE(aligned16(H) && aligned16(S) && aligned16(H_out) && (b == nullptr || aligned16(b)), NT_EINVAL,
+               "bf16 with h > 512 needs 16-byte aligned feature pointers");
+    if (aact == NT_ACT_IDENTITY)
+      NT_BF_DISPATCH_A(act, return (launch_upd_wide<A_, 1>(H, S, src, rev, Wp, b, V, E, h, residual, act,
+                                                           alpha, H_out, ntiles, agg, stream)));
+    else
+      NT_BF_DISPATCH_A(act, return (launch_upd_wide<A_, 2>(H, S, src, rev, Wp, b, V, E, h, residual, act,
+                                                           alpha, H_out, ntiles, agg, stream)));
+  }
   if (aact == NT_ACT_IDENTITY)
     NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 8, 1>(H, S, src, rev, Wp, b, V, E, h, residual,
                                                           act, alpha, H_out, ntiles, agg, stream)));

@@ -20,11 +20,15 @@ size_t bf16_image_bytes(int64_t h);
 int pack_weight_bf16(const void* W, int64_t nlayers, int64_t h, int64_t layer_stride_bytes, void* Wp,
                      hipStream_t stream);
 
+// hidden sizes of the bf16 layer kernel: any h <= 512 (scalar rows when h % 8 != 0); above that the
+// column-pass kernel takes whole 16-B pieces only
+#define NT_BF16_H_RULE "bf16 needs h <= 512, or h % 8 == 0 and h <= 8192"
+bool bf16_update_supported(int64_t h);
 int launch_update_bf16(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                        const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
                        int act, float alpha, void* H_out, hipStream_t stream);
 
-// fused with the aggregation its output feeds (tile plan of nt_dmpnn_tile_plan); h % 8 == 0, <= 512
+// fused with the aggregation its output feeds (tile plan of nt_dmpnn_tile_plan); h % 8 == 0, <= 8192
 bool bf16_fused_supported(int64_t h);
 int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                              const void* Wp, const void* b, int64_t V, int64_t E, int64_t h,

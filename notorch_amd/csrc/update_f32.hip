@@ -566,8 +566,10 @@ extern "C" int nt_dmpnn_pack_weight(const void* W, int64_t nlayers, int64_t h, i
   using namespace nt;
   clear_error();
   NT_REQUIRE(dtype == NT_F32 || dtype == NT_BF16, NT_EUNSUPPORTED, "dtype must be NT_F32 or NT_BF16");
-  NT_REQUIRE(nlayers >= 0 && h > 0 && (dtype == NT_F32 || h <= 512) && h <= 8192, NT_EINVAL,
-             "bad sizes (1 <= h <= 512 for bf16, <= 8192 for fp32)");
+  NT_REQUIRE(nlayers >= 0 && h > 0 && (dtype == NT_BF16 || h <= 8192), NT_EINVAL,
+             "bad sizes (1 <= h <= 8192)");
+  NT_REQUIRE(dtype == NT_F32 || bf16_update_supported(h), NT_EUNSUPPORTED,
+             NT_BF16_H_RULE);
   if (nlayers == 0) return NT_OK;
   NT_REQUIRE(W && Wp && aligned16(Wp), NT_EINVAL, "NULL or misaligned pointer");
   if (dtype == NT_BF16)
@@ -674,7 +676,14 @@ extern "C" int nt_dmpnn_update(const void* H, const void* S, const int64_t* src,
   clear_error();
   NT_REQUIRE(dtype == NT_F32 || dtype == NT_BF16, NT_EUNSUPPORTED, "dtype must be NT_F32 or NT_BF16");
   NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
-  NT_REQUIRE(V >= 0 && E >= 0 && h > 0 && h <= 512, NT_EINVAL, "bad sizes (1 <= h <= 512)");
+  NT_REQUIRE(V >= 0 && E >= 0 && h > 0, NT_EINVAL, "bad sizes (h >= 1)");
+  // fp32: update_fk_kernel's plain mode (h % 4 == 0) loops over column chunks up to h = 8192; the
+  // exact fp32 tile kernel (h % 4 != 0) stops at 512.  bf16: the column-pass kernel above 512.
+  if (dtype == NT_BF16)
+    NT_REQUIRE(bf16_update_supported(h), NT_EUNSUPPORTED, NT_BF16_H_RULE);
+  else
+    NT_REQUIRE(h <= 512 || (h % 4 == 0 && h <= 8192), NT_EUNSUPPORTED,
+               "fp32 needs h <= 512, or h % 4 == 0 and h <= 8192");
   if (E == 0) return NT_OK;
   NT_REQUIRE(H && S && src && rev && Wp && H_out, NT_EINVAL, "NULL pointer");
   NT_REQUIRE(H != H_out, NT_EINVAL, "H_out must not alias H");
@@ -754,7 +763,7 @@ extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t
   NT_REQUIRE(V >= 0 && E >= 0 && E < (int64_t(1) << 31) && V < (int64_t(1) << 31) && h > 0, NT_EINVAL,
              "bad sizes");
   NT_REQUIRE(dtype == NT_BF16 ? bf16_fused_supported(h) : (h % 4 == 0 && h <= 8192), NT_EUNSUPPORTED,
-             "update_fused needs h % 4 == 0 (fp32), h % 8 == 0 and h <= 512 (bf16)");
+             "update_fused needs h % 4 == 0 (fp32) or h % 8 == 0 (bf16), h <= 8192");
   if (E == 0) return NT_OK;
   NT_REQUIRE(H && S && src && rev && Wp && H_out, NT_EINVAL, "NULL pointer");
   NT_REQUIRE(H != H_out && (S_out == nullptr || S_out != S), NT_EINVAL, "outputs alias inputs");
@@ -796,8 +805,8 @@ extern "C" int nt_dmpnn_dense_matmul(const void* X, int64_t M, int64_t h, const 
   clear_error();
   NT_REQUIRE(dtype == NT_F32 || dtype == NT_BF16, NT_EUNSUPPORTED, "nt_dmpnn_dense_matmul: fp32 or bf16");
   NT_REQUIRE(M >= 0 && M < (int64_t(1) << 31) && h > 0, NT_EINVAL, "bad sizes");
-  if (dtype == NT_BF16) {  // the bf16 layer kernel without gathers, residual or bias (h <= 512)
-    NT_REQUIRE(h <= 512, NT_EUNSUPPORTED, "nt_dmpnn_dense_matmul: bf16 needs h <= 512");
+  if (dtype == NT_BF16) {  // the bf16 layer kernel without gathers, residual or bias
+    NT_REQUIRE(bf16_update_supported(h), NT_EUNSUPPORTED, NT_BF16_H_RULE);
     if (M == 0) return NT_OK;
     NT_REQUIRE(X && Wp && out && X != out, NT_EINVAL, "NULL pointer or out aliases X");
     if (bf16_fk(h) && aligned16(X) && aligned16(out)) {  // the bf16 layer kernel's dense mode

@@ -452,8 +452,9 @@ def packed_weight_numel(h: int, dtype: torch.dtype = torch.float32) -> int:
 def pack_weights(W: Tensor, *, fk_only: bool = False) -> Tensor:
     """Pack one nn.Linear weight [h, h] (or a stack [L, h, h]) into the MFMA fragment image of its
     dtype (fp32: the two-part fp16 image of the fp32 layer kernel plus the older bf16-split images;
-    bf16: one bf16 fragment image).  The image is an opaque float32-typed buffer.  fk_only (fp32):
-    only the part nt_dmpnn_update_fused / dense_matmul read (nt_dmpnn_pack_weight_fk)."""
+    bf16: one bf16 fragment image, h <= 512 or h % 8 == 0 up to 8192).  The image is an opaque
+    float32-typed buffer.  fk_only (fp32): only the part nt_dmpnn_update_fused / dense_matmul read
+    (nt_dmpnn_pack_weight_fk)."""
     dev = _require_device(W)
     code = _require_feat("weight", W)
     if W.dim() == 2:
@@ -542,9 +543,9 @@ def dmpnn_update(
 
 def fused_supported(V: int, E: int, h: int, dtype: torch.dtype = torch.float32) -> bool:
     """Shapes nt_dmpnn_update_fused accepts: the fp32 fk kernel (h % 4 == 0, h <= 8192) or the bf16
-    tile kernel (h % 8 == 0, h <= 512)."""
+    tile kernel (h % 8 == 0, h <= 8192; above 512 its column-pass variant)."""
     if dtype == torch.bfloat16:
-        return h % 8 == 0 and 8 <= h <= 512 and E < 2**31
+        return h % 8 == 0 and 8 <= h <= 8192 and E < 2**31
     return (dtype == torch.float32 and h % 4 == 0 and 4 <= h <= 8192 and E * h // 4 < 2**31
             and V * h // 4 < 2**31 and E < 2**31 and V < 2**31)
 
@@ -816,8 +817,8 @@ def dense_matmul(X: Tensor, Wp: Tensor, out: Tensor | None = None, *, kernel: st
     """X @ W^T for the packed image Wp of W: the layer GEMM alone.  With Wp = pack_weights(W.t()) it is
     the backward's dA = G @ W.  fp32 (h % 4 == 0), kernel = "fk": the fp16x3 layer kernel in dense
     mode (amax: 2 device floats whose [1] >= max|X|, else nt_absmax first; any h); "pk": the bf16x6
-    persistent kernel (h <= 304).  bf16 (h <= 512): the bf16 layer kernel without gathers (fp32
-    accumulate, one rounding)."""
+    persistent kernel (h <= 304).  bf16 (h <= 512, or h % 8 == 0 up to 8192): the bf16 layer kernel
+    without gathers (fp32 accumulate, one rounding)."""
     dev = _require_device(X, Wp, out, amax)
     code = _require_feat("X", X)
     M, h = X.shape
@@ -826,8 +827,8 @@ def dense_matmul(X: Tensor, Wp: Tensor, out: Tensor | None = None, *, kernel: st
     if out is None:
         out = torch.empty_like(X)
     if code == NT_BF16:
-        if h > 512:
-            raise ValueError("dense_matmul: bf16 needs h <= 512")
+        if h > 512 and (h % 8 or h > 8192):
+            raise ValueError("dense_matmul: bf16 needs h <= 512, or h % 8 == 0 and h <= 8192")
         _run(dev, _lib.load().nt_dmpnn_dense_matmul, _ptr(X), M, h, _ptr(Wp), NT_BF16, None, None, _ptr(out),
              _stream(dev))
         return out

@@ -909,7 +909,10 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
         Gu = Gu.contiguous()
         fk_dense = fp32 and K.fused_supported(V, E, h, Gu.dtype)
         fk_wgrad = fp32 and wgrad == "kernel" and h <= 320
-        bf16_kernels = Gu.dtype == torch.bfloat16 and wgrad != "library" and h <= 512 and h % 8 == 0
+        # bf16: dA runs on the layer kernel's dense mode at every h it supports; the weight-gradient
+        # kernel stages all of G's columns and stops at h = 512 (library GEMM above)
+        bf16_da = Gu.dtype == torch.bfloat16 and wgrad != "library" and K.fused_supported(V, E, h, Gu.dtype)
+        bf16_wgrad = bf16_da and h <= 512
         gmax = gmax_cur if drop is None else None  # dropout rescales G: its max is taken afresh
         if (fk_dense or fk_wgrad) and gmax is None:  # max|G|: the split scale of both fp16-split kernels
             gmax = torch.zeros(2, dtype=torch.float32, device=Gu.device)
@@ -926,7 +929,7 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
                     K.absmax(S_l.contiguous(), am[1:2])
             dWs[l], dbs[l] = K.weight_grad(Gu, H_l.contiguous(), S_l.contiguous(), src, rev, act=act,
                                            amax_G=None if am is None else gmax[1:2], amax_HS=am)
-        elif bf16_kernels:  # A rounded to bf16 in the kernel as the forward's message; fp32 partials
+        elif bf16_wgrad:  # A rounded to bf16 in the kernel as the forward's message; fp32 partials
             dW32, db32 = K.weight_grad(Gu, H_l.contiguous(), S_l.contiguous(), src, rev, act=act)
             dWs[l], dbs[l] = dW32.to(Gu.dtype), db32.to(Gu.dtype)
         else:
@@ -950,7 +953,7 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
         else:
             if fk_dense:
                 dA = K.dense_matmul(Gu, packed_transpose(weights[l]), amax=gmax)
-            elif bf16_kernels and os.environ.get("NT_BF16_DA", "kernel") == "kernel":  # the bf16 layer kernel
+            elif bf16_da and os.environ.get("NT_BF16_DA", "kernel") == "kernel":  # the bf16 layer kernel
                 dA = K.dense_matmul(Gu, K.pack_weights(W.t().contiguous()))  # without gathers
             else:
                 dA = torch.mm(Gu, W)

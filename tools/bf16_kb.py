@@ -57,9 +57,16 @@ def main():
     torch.cuda.synchronize()
     res = [timeit(f) for _ in range(a.rounds)]
     med = statistics.median(res)
+    # unique rows (what HBM has to deliver) and what the CUs request: above h = 512 the two gathered
+    # rows are read once per column pass of 512 (repeats from L2), and every tile reads the whole
+    # weight image
     alg = (4 * E * h * 2 + V * h * 2) / (med * 1e-6) / 1e12
+    passes = (h + 511) // 512
+    req = ((2 + 2 * passes) * E * h * 2 + V * h * 2 + plan[1] * K.packed_weight_numel(h, bf) * 4) / (med * 1e-6) / 1e12
+    tf = 2 * E * h * h / (med * 1e-6) / 1e12
     print(f"{a.kind}-{a.mols} V={V} E={E} h={h} rows={rows}: median {med:7.1f} us  "
-          f"(~{alg:.2f} TB/s of H/S/H' rows)  lib={os.environ.get('NT_LIB', '')}")
+          f"min {min(res):7.1f} max {max(res):7.1f}  (~{alg:.2f} TB/s of H/S/H' rows, {req:.2f} TB/s requested "
+          f"incl. {passes}x gathers and W per tile, {tf:.0f} TFLOP/s)  lib={os.environ.get('NT_LIB', '')}")
 
 
 if __name__ == "__main__":
