@@ -524,7 +524,13 @@ NT_API int nt_dmpnn_dense_matmul(const void* X, int64_t M, int64_t h, const void
  *   A[e] = S[src[e]] - act(H[rev[e]])   (chemprop.py:40; src = rev = NULL: A[e] = S[e], H unused)
  *   dW = G^T A  (h x h),   db = sum_e G[e]  (db_out may be NULL)
  * Split-K bf16x6 MFMA kernel (fp32-accurate), deterministic (partials reduced in fixed order).
- * workspace: device buffer of at least nt_dmpnn_weight_grad_workspace(E, h) bytes.  fp32 only. */
+ * workspace: device buffer of at least nt_dmpnn_weight_grad_workspace(E, h) bytes.
+ * bf16 (src and rev required; an even h <= 512, or h % 8 == 0 and h <= 8192, else NT_EUNSUPPORTED):
+ * A is rounded to bf16 once as nt_dmpnn_message writes it, one bf16 MFMA per tile with fp32
+ * partials, dW_out and db_out in fp32.  Up to h = 512 one workgroup stages all of G's columns per
+ * 128-column block of A; above, dW is tiled 256 x 256, G is read ceil(h / 256) times and G, H and
+ * S must be 16-byte aligned.  Same workspace query, same fixed-order reduction (two calls are
+ * bit-identical). */
 NT_API int64_t nt_dmpnn_weight_grad_workspace(int64_t E, int64_t h);
 NT_API int nt_dmpnn_weight_grad(const void* G, const void* H, const void* S, const int64_t* src,
                                 const int64_t* rev, int64_t V, int64_t E, int64_t h, int act,

@@ -868,6 +868,206 @@ __global__ void __launch_bounds__(512, 1) wgrad_bf16_kernel(WbArgs a) {
   }
 }
 
+// wgrad_bf16_wide_kernel (bf16 storage, 512 < h <= 8192, h % 8 == 0, gathered A): the same dW, db
+// and message formation as wgrad_bf16_kernel, with dW tiled in both dimensions: one 512-thread
+// workgroup per (edge chunk, 256-column block of G, 256-column block of A).  Per 32-edge step the
+// block's G and A rows are staged in 16-B pieces (8 columns: h % 8 == 0 keeps a piece aligned and
+// wholly inside or outside h) into a double-buffered [edge][column] LDS slab (2 x 2 x 17 KiB, rows
+// padded to 544 B, one barrier per step) and read back as MFMA operands by the transposing LDS read;
+// wave w owns i-tiles 8 (w % 2) .. +8 and j-tiles 4 (w / 2) .. +4 of the block (32 accumulators, as
+// the narrow kernel).  G is read and A formed ceil(h / 256) times each.  db of an i-block's columns
+// comes from the j-block-0 workgroups of that i-block.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+constexpr int kXI = 256;                // G columns per block
+constexpr int kXJ = 256;                // A columns per block (= kXI: one row stride for both slabs)
+constexpr int kXRS = 2 * kXI + 32;      // LDS row stride in bytes: 256 bf16 and 32 B of padding, which
+                                        // puts the 4 edges of a transposing read on different banks
+constexpr int kXPart = kK * kXRS;       // one operand's slab (17 KiB)
+constexpr int kXBuf = 2 * kXPart;       // G slab, A slab
+constexpr int kXLds = 2 * kXBuf;
+constexpr int kXMaxH = 8192;
+
+struct WxArgs {
+  const uint16_t* G;
+  const uint16_t* H;
+  const uint16_t* S;
+  const int64_t* src;
+  const int64_t* rev;
+  int64_t E, h;
+  int iblocks, jblocks, ksplit, chunk_steps, xcds;
+  float alpha;
+  int act;
+  float* part;     // [ksplit][h][h]
+  float* part_db;  // [ksplit][h] or NULL
+};
+
+template <int ACT>
+__global__ void __launch_bounds__(512, 1) wgrad_bf16_wide_kernel(WxArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int nb = gridDim.x;
+  int w = blockIdx.x;
+  if (a.xcds > 1 && nb % a.xcds == 0) w = (w % a.xcds) * (nb / a.xcds) + w / a.xcds;
+  const int tiles = a.iblocks * a.jblocks;
+  const int y = w / tiles, tile = w - y * tiles;
+  const int ib = tile / a.jblocks, jb = tile - ib * a.jblocks;
+  const int64_t h = a.h, i0 = (int64_t)ib * kXI, j0 = (int64_t)jb * kXJ;
+  const int64_t e_beg = (int64_t)y * a.chunk_steps * kK;
+  const int64_t e_end0 = e_beg + (int64_t)a.chunk_steps * kK;
+  const int64_t e_end = e_end0 < a.E ? e_end0 : a.E;
+  const int nsteps = e_end > e_beg ? (int)((e_end - e_beg + kK - 1) / kK) : 0;
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const bool want_db = a.part_db != nullptr && jb == 0;
+
+  // Staging: every operand row of a slab is 32 pieces of 16 B (8 columns).  Thread t owns piece
+  // t % 32 of rows t / 32 and t / 32 + 16: three 16-B loads per row (G, S[src], H[rev]).  Dword loads
+  // (a column pair per lane) ran at a quarter of this: the texture addresser takes 4 lanes per clock
+  // whatever their width.  Pieces go to LDS as loaded, [edge][column]; the MFMA operands (8 consecutive
+  // edges of one column per lane) come back through the transposing LDS read.
+  const int oct = t & 31, hi = lane >> 5;
+  const int row0 = 2 * wave + hi;  // my rows of a slab: row0, row0 + 16
+  const bool oki = i0 + 8 * oct < h, okj = j0 + 8 * oct < h;
+  const int64_t ic = oki ? i0 + 8 * oct : 0, jc = okj ? j0 + 8 * oct : 0;
+  float dbacc[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) dbacc[c] = 0.f;
+
+  // one vector load per wave and step: lane k < 4 the src of row 2 wave + (k & 1) + 16 (k >> 1), lanes
+  // 4 .. 7 its rev
+  auto load_idx = [&](int s) __attribute__((always_inline)) -> int {
+    int64_t e = e_beg + (int64_t)s * kK + 2 * wave + (lane & 1) + 16 * ((lane >> 1) & 1);
+    e = e < e_end ? e : e_end - 1;
+    return lane >= 8 ? 0 : (int)(lane < 4 ? a.src[e] : a.rev[e]);
+  };
+  uint4 xg[2], xs[2], xh[2];  // raw pieces of the step in flight
+  int64_t eb_cur = 0;
+  auto load = [&](int s, int idxv) __attribute__((always_inline)) {
+    const int64_t eb = e_beg + (int64_t)s * kK;
+    eb_cur = eb;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      int64_t e = eb + row0 + 16 * m;
+      e = e < e_end ? e : e_end - 1;
+      const int s0 = __builtin_amdgcn_readlane(idxv, 2 * m), s1 = __builtin_amdgcn_readlane(idxv, 2 * m + 1);
+      const int r0 = __builtin_amdgcn_readlane(idxv, 4 + 2 * m), r1 = __builtin_amdgcn_readlane(idxv, 5 + 2 * m);
+      const int64_t se = hi ? s1 : s0, re = hi ? r1 : r0;
+      xg[m] = *reinterpret_cast<const uint4*>(a.G + e * h + ic);
+      xs[m] = *reinterpret_cast<const uint4*>(a.S + se * h + jc);
+      xh[m] = *reinterpret_cast<const uint4*>(a.H + re * h + jc);
+    }
+  };
+  auto store = [&](char* buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const int row = row0 + 16 * m;
+      const bool in = eb_cur + row < e_end;
+      const uint32_t mg = (in && oki) ? ~0u : 0u, ma = (in && okj) ? ~0u : 0u;
+      uint4 g = xg[m];
+      g.x &= mg; g.y &= mg; g.z &= mg; g.w &= mg;
+      if (want_db) {
+        const uint32_t w[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          dbacc[2 * c] += bfu(w[c] & 0xffffu);
+          dbacc[2 * c + 1] += __uint_as_float(w[c] & 0xffff0000u);
+        }
+      }
+      *reinterpret_cast<uint4*>(buf + row * kXRS + oct * 16) = g;
+      const uint32_t sw[4] = {xs[m].x, xs[m].y, xs[m].z, xs[m].w};
+      const uint32_t hw[4] = {xh[m].x, xh[m].y, xh[m].z, xh[m].w};
+      bf16x8 av;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float u0 = bfu(sw[c] & 0xffffu) - act_t<ACT>(bfu(hw[c] & 0xffffu), a.act, a.alpha);
+        const float u1 = __uint_as_float(sw[c] & 0xffff0000u) -
+                         act_t<ACT>(__uint_as_float(hw[c] & 0xffff0000u), a.act, a.alpha);
+        av[2 * c] = (__bf16)__uint_as_float(__float_as_uint(u0) & ma);  // out of range: exact +0
+        av[2 * c + 1] = (__bf16)__uint_as_float(__float_as_uint(u1) & ma);
+      }
+      *reinterpret_cast<bf16x8*>(buf + kXPart + row * kXRS + oct * 16) = av;
+    }
+  };
+
+  const int fr = lane & 15, g16 = lane >> 4;
+  const int wi = wave & 1, wj = wave >> 1;  // i-tiles 8 wi .. 8 wi + 7, j-tiles 4 wj .. 4 wj + 3
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int x = 0; x < 8; ++x)
+#pragma unroll
+    for (int z = 0; z < 4; ++z) acc[x][z] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // waves whose i-tiles or j-tiles all lie past h skip the MFMAs (a whole wave: the transposing
+  // read needs every lane)
+  const bool active = i0 + 16 * 8 * wi < h && j0 + 16 * 4 * wj < h;
+  // transposing read of a 4-edge x 16-column block per 16 lanes: lane 4 q + p of the group gives the
+  // address of edge q, columns 4 p .. 4 p + 3, and receives column (lane % 16) of the 4 edges.  Two
+  // reads (edges 8 g16 .. + 3 and + 4 .. + 7) make the 8 consecutive edges of an MFMA operand.
+  const int tr_off = (8 * g16 + (fr >> 2)) * kXRS + 8 * (fr & 3);
+  typedef bf16x4 __attribute__((address_space(3))) * lds4_t;
+  auto frag = [&](const char* base, int tile) __attribute__((always_inline)) -> bf16x8 {
+    const char* p = base + tr_off + 32 * tile;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4_t)p);
+    const bf16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4_t)(p + 4 * kXRS));
+    return __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  auto mfma = [&](const char* gb) __attribute__((always_inline)) {
+    if (!active) return;
+    const char* ab = gb + kXPart;
+    bf16x8 fb[4];
+#pragma unroll
+    for (int z = 0; z < 4; ++z) fb[z] = frag(ab, 4 * wj + z);
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+      const bf16x8 fa = frag(gb, 8 * wi + x);
+#pragma unroll
+      for (int z = 0; z < 4; ++z) acc[x][z] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[z], acc[x][z], 0, 0, 0);
+    }
+  };
+
+  // the pieces of step s + 1 are in flight while slab s is multiplied
+  int idx_next = 0;
+  if (nsteps > 0) {
+    load(0, load_idx(0));
+    if (nsteps > 1) idx_next = load_idx(1);
+    store(lds);
+  }
+  __syncthreads();
+  for (int s = 0; s < nsteps; ++s) {
+    const bool more = s + 1 < nsteps;
+    if (more) {
+      load(s + 1, idx_next);
+      if (s + 2 < nsteps) idx_next = load_idx(s + 2);
+    }
+    mfma(lds + (s & 1) * kXBuf);
+    if (more) store(lds + ((s + 1) & 1) * kXBuf);
+    __syncthreads();  // one barrier: the next slab is written, this one is read by every wave
+  }
+
+  float* P = a.part + (int64_t)y * h * h;
+#pragma unroll
+  for (int x = 0; x < 8; ++x)
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+      const int64_t col = j0 + 16 * (4 * wj + z) + fr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t row = i0 + 16 * (8 * wi + x) + 4 * g16 + q;
+        if (row < h && col < h) P[row * h + col] = acc[x][z][q];
+      }
+    }
+  if (want_db) {  // fixed-order column sums over the 16 threads of a piece column (deterministic)
+    float* red = reinterpret_cast<float*>(lds);  // the slabs are dead after the last barrier
+#pragma unroll
+    for (int c = 0; c < 8; ++c) red[(t >> 5) * kXI + 8 * oct + c] = dbacc[c];
+    __syncthreads();
+    if (t < kXI && i0 + t < h) {
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sum += red[k * kXI + t];
+      a.part_db[(int64_t)y * h + i0 + t] = sum;
+    }
+  }
+}
+
 // dW and db partials reduced in one launch: index i < n1 sums part[y][i] into out1[i], the rest sums
 // part_db[y][i - n1] into out2, each in ascending y (fixed order: deterministic)
 __global__ void __launch_bounds__(256) wgrad_reduce2_kernel(const float* __restrict__ part, int64_t n1,
@@ -942,6 +1142,22 @@ WPlan make_wide_plan(int64_t E, int64_t h, int jcols = kWJ) {
   return p;
 }
 
+// the bf16 wide kernel: one workgroup per CU, ksplit = CUs / (i-blocks x j-blocks) chunks (at least
+// one; from h = 4096 the tiles alone fill the machine).  Never more chunks than make_wide_plan's.
+WPlan make_bf16_wide_plan(int64_t E, int64_t h) {
+  WPlan p;
+  const int64_t tiles = ((h + kXI - 1) / kXI) * ((h + kXJ - 1) / kXJ);
+  const int64_t steps = (E + kK - 1) / kK;
+  int64_t ks = (cu_count() > 0 ? cu_count() : 256) / tiles;
+  if (ks < 1) ks = 1;
+  if (ks > steps) ks = steps > 0 ? steps : 1;
+  p.chunk_steps = (int)((steps + ks - 1) / ks);
+  if (p.chunk_steps < 1) p.chunk_steps = 1;
+  p.ksplit = (int)((steps + p.chunk_steps - 1) / p.chunk_steps);
+  if (p.ksplit < 1) p.ksplit = 1;
+  return p;
+}
+
 }  // namespace
 
 int xcd_count();  // csrc/update_ps.hip: the current device's XCD count, queried once per device
@@ -953,6 +1169,10 @@ extern "C" int64_t nt_dmpnn_weight_grad_workspace(int64_t E, int64_t h) {
   const nt::WPlan q = nt::make_wide_plan(E, h), f = nt::make_wide_plan(E, h, nt::kFJ);
   int64_t ks = p.ksplit > q.ksplit ? p.ksplit : q.ksplit;  // every kernel fits
   ks = ks > f.ksplit ? ks : f.ksplit;
+  if (h > nt::kBI) {  // the bf16 wide kernel's plan (never above the others: see make_bf16_wide_plan)
+    const nt::WPlan x = nt::make_bf16_wide_plan(E, h);
+    ks = ks > x.ksplit ? ks : x.ksplit;
+  }
   return ks * (h * h + h) * (int64_t)sizeof(float);
 }
 
@@ -965,8 +1185,9 @@ extern "C" int nt_dmpnn_weight_grad(const void* G, const void* H, const void* S,
   NT_REQUIRE(dtype == NT_F32 || dtype == NT_BF16, NT_EUNSUPPORTED, "nt_dmpnn_weight_grad: fp32 or bf16");
   NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
   NT_REQUIRE(V >= 0 && E >= 0 && h > 0, NT_EINVAL, "bad sizes");
-  NT_REQUIRE(dtype == NT_F32 || (h <= kBI && h % 2 == 0 && src && rev), NT_EUNSUPPORTED,
-             "nt_dmpnn_weight_grad: bf16 needs h <= 512, h even, src and rev");
+  NT_REQUIRE(dtype == NT_F32 || (((h <= kBI && h % 2 == 0) || (h % 8 == 0 && h <= kXMaxH)) && src && rev),
+             NT_EUNSUPPORTED,
+             "nt_dmpnn_weight_grad: bf16 needs src and rev, and an even h <= 512 or h % 8 == 0 and h <= 8192");
   // row indices are narrowed to int for the lane broadcasts
   NT_REQUIRE(V < ((int64_t)1 << 31) && E < ((int64_t)1 << 31), NT_EUNSUPPORTED,
              "nt_dmpnn_weight_grad: V and E must be < 2^31");
@@ -998,6 +1219,36 @@ extern "C" int nt_dmpnn_weight_grad(const void* G, const void* H, const void* S,
   a.act = act;
   a.part = (float*)workspace;
   a.part_db = db_out ? a.part + (int64_t)p.ksplit * h * h : nullptr;
+  if (dtype == NT_BF16 && h > kBI) {  // dW tiled in both dimensions
+    NT_REQUIRE(((uintptr_t)G | (uintptr_t)H | (uintptr_t)S) % 16 == 0, NT_EINVAL,
+               "nt_dmpnn_weight_grad: bf16 h > 512 needs 16-byte aligned G, H and S");
+    const WPlan q = make_bf16_wide_plan(E, h);
+    WxArgs b;
+    b.G = (const uint16_t*)G;
+    b.H = (const uint16_t*)H;
+    b.S = (const uint16_t*)S;
+    b.src = src;
+    b.rev = rev;
+    b.E = E;
+    b.h = h;
+    b.iblocks = (int)((h + kXI - 1) / kXI);
+    b.jblocks = (int)((h + kXJ - 1) / kXJ);
+    b.ksplit = q.ksplit;
+    b.chunk_steps = q.chunk_steps;
+    b.xcds = xcd_count();
+    b.alpha = act_alpha;
+    b.act = act;
+    b.part = (float*)workspace;
+    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
+    const int grid = b.iblocks * b.jblocks * q.ksplit;
+    auto kern = act == NT_ACT_IDENTITY ? wgrad_bf16_wide_kernel<NT_ACT_IDENTITY>
+                : act == NT_ACT_RELU   ? wgrad_bf16_wide_kernel<NT_ACT_RELU>
+                                       : wgrad_bf16_wide_kernel<-1>;
+    NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kXLds));
+    kern<<<grid, 512, kXLds, stream>>>(b);
+    NT_LAUNCH_CHECK();
+    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
+  }
   if (dtype == NT_BF16) {
     const WPlan q = make_wide_plan(E, h);
     WbArgs b;

@@ -854,13 +854,17 @@ def weight_grad(G: Tensor, H: Tensor | None, S: Tensor, src: Tensor | None, rev:
     """(dW, db) = (G^T A, sum_e G[e]) with A[e] = S[src e] - act(H[rev e]) formed on the fly
     (src = rev = None: A = S).  Split-K, deterministic.  fp32: with amax_G (1 device float >= max|G|)
     and amax_HS (2 floats >= max|H|, max|S|), h <= 320 and src / rev given, the two-part fp16 kernel
-    (nt_dmpnn_weight_grad_fk); else the bf16x6 kernel.  bf16 (h <= 512, even, src / rev given): A
-    rounded to bf16 as the forward's message, one bf16 MFMA per tile; dW and db come back in fp32."""
+    (nt_dmpnn_weight_grad_fk); else the bf16x6 kernel.  bf16 (src / rev given; an even h <= 512, or
+    h % 8 == 0 up to 8192 on the kernel that tiles dW in both dimensions): A rounded to bf16 as the
+    forward's message, one bf16 MFMA per tile; dW and db come back in fp32."""
     dev = _require_device(G, H, S, src, rev, amax_G, amax_HS)
     code = _require_feat("G", G)
     _require_feat("S", S, G.dtype)
-    if code == NT_BF16 and (src is None or G.shape[1] > 512 or G.shape[1] % 2):
-        raise ValueError("weight_grad: bf16 needs src / rev_index and an even h <= 512")
+    if code == NT_BF16:
+        hb = G.shape[1]
+        if src is None or not ((hb <= 512 and hb % 2 == 0) or (hb % 8 == 0 and hb <= 8192)):
+            raise ValueError("weight_grad: bf16 needs src / rev_index, and an even h <= 512 or h % 8 == 0 "
+                             "and h <= 8192")
     E, h = G.shape
     if (src is None) != (rev is None):
         raise ValueError("weight_grad: pass both src and rev_index or neither")
@@ -876,6 +880,11 @@ def weight_grad(G: Tensor, H: Tensor | None, S: Tensor, src: Tensor | None, rev:
     for n_, t in (("G", G), ("H", H), ("S", S)):
         if t is not None and not t.is_contiguous():
             raise ValueError(f"weight_grad: {n_} must be contiguous")
+    if E == 0 and code == NT_BF16:
+        # empty sums; empty index tensors have no address to hand to the entry point, which asks
+        # bf16 callers for src and rev before it looks at E
+        return (torch.zeros(h, h, dtype=torch.float32, device=dev),
+                torch.zeros(h, dtype=torch.float32, device=dev) if bias else None)
     lib = _lib.load()
     # the workspace is sized by the plan of the launch device (its CU count): query under its guard
     if dev.index is not None and dev.index != torch.cuda.current_device():

@@ -58,6 +58,10 @@ _FUSED_DA = os.environ.get("NT_FUSED_DA", "1") != "0"
 # fp32 weight gradient: "kernel" (nt_dmpnn_weight_grad_fk for h <= 320, else nt_dmpnn_weight_grad),
 # "kernel6" (nt_dmpnn_weight_grad, bf16x6) or "library" (message + split-K library GEMM)
 _WGRAD_DEFAULT = "kernel"
+# bf16 weight gradient: the largest h block_backward sends to K.weight_grad (which accepts every
+# h % 8 == 0 up to 8192); above it the message + split-K library GEMM.  Measured: the
+# kernel wins at 640 and 1024, is 14 % behind the library route at 2048 and 19 % at 4096.
+BF16_WGRAD_MAX_H = 2048
 
 # Optional per-launch timer for the dominant kernel (bench.py sets it): a list that receives
 # (start, end) torch.cuda.Event pairs recorded on the launch stream around every nt_dmpnn_update.
@@ -909,10 +913,11 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
         Gu = Gu.contiguous()
         fk_dense = fp32 and K.fused_supported(V, E, h, Gu.dtype)
         fk_wgrad = fp32 and wgrad == "kernel" and h <= 320
-        # bf16: dA runs on the layer kernel's dense mode at every h it supports; the weight-gradient
-        # kernel stages all of G's columns and stops at h = 512 (library GEMM above)
+        # bf16: dA runs on the layer kernel's dense mode at every h it supports, dW on the
+        # weight-gradient kernel (above h = 512 its variant that tiles dW in both dimensions) up to
+        # BF16_WGRAD_MAX_H, on the library GEMM above
         bf16_da = Gu.dtype == torch.bfloat16 and wgrad != "library" and K.fused_supported(V, E, h, Gu.dtype)
-        bf16_wgrad = bf16_da and h <= 512
+        bf16_wgrad = bf16_da and h <= BF16_WGRAD_MAX_H
         gmax = gmax_cur if drop is None else None  # dropout rescales G: its max is taken afresh
         if (fk_dense or fk_wgrad) and gmax is None:  # max|G|: the split scale of both fp16-split kernels
             gmax = torch.zeros(2, dtype=torch.float32, device=Gu.device)

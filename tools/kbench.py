@@ -1,6 +1,7 @@
 """Micro-benchmark of the individual fp32 forward kernels on one qm9-shaped batch (device time via
 torch.cuda events, interleaved rounds in one process).  Also the driver for the per-kernel PMC passes
-(tools/pmc_update.sh).  Usage: python tools/kbench.py [--mols 4096] [--h 300] [--only fk_fused,init]"""
+(tools/pmc_update.sh).  Usage: python tools/kbench.py [--mols 4096] [--h 300] [--only fk_fused,init]
+--only wgrad_bf16 [--kind zinc --h 1024]: the bf16 weight-gradient kernel beside the library route."""
 import argparse
 import os
 import statistics
@@ -25,6 +26,57 @@ def timeit(fn, reps=20):
     return statistics.median(ts), min(ts)
 
 
+HBM_PEAK = 8e12        # B/s (spec)
+BF16_MFMA_PEAK = 2.5e15  # flop/s, dense (spec)
+
+
+def wgrad_bf16(G, h, rounds):
+    """bf16 weight gradient of one layer on the batch's graph: K.weight_grad (one launch + the
+    partial reduction) beside the library route (dmpnn_message + split-K library GEMM + column sum),
+    interleaved rounds.  Prints each median and the kernel's algorithmic bytes and roofs."""
+    from notorch_amd.nn.gnn import _engine
+
+    V, E = G.num_nodes, G.num_edges
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    bf = torch.bfloat16
+    Gr = torch.randn(E, h, device="cuda", generator=gen).to(bf)
+    H = torch.randn(E, h, device="cuda", generator=gen).to(bf)
+    S = torch.randn(V, h, device="cuda", generator=gen).to(bf)
+    src, rev = G.edge_index[0].contiguous(), G.rev_index
+    relu = K.act_code(torch.nn.ReLU())
+
+    def library():
+        A = K.dmpnn_message(H, S, src, rev, act=relu)
+        return _engine._weight_grad(Gr, A), Gr.sum(0)
+
+    fns = {"wgrad_bf16": lambda: K.weight_grad(Gr, H, S, src, rev, act=relu), "wgrad_bf16_library": library}
+    dW, db = fns["wgrad_bf16"]()
+    dWl, dbl = library()
+    torch.cuda.synchronize()
+    scale = dW.abs().max().item()
+    print(f"V={V} E={E} h={h} bf16: max |dW kernel - dW library| / max|dW| = "
+          f"{(dW - dWl.float()).abs().max().item() / scale:.2e}")
+    res = {n: [] for n in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            res[name].append(timeit(f, 10))
+    # the kernel's traffic: above h = 512 dW is tiled 256 x 256 (G is read once per j-block and the two
+    # gathers once per i-block), up to 512 all of G per 128-column block of A and the gathers once
+    ib, jb = ((h + 255) // 256, (h + 255) // 256) if h > 512 else (1, (h + 127) // 128)
+    once = 3 * E * h * 2
+    loaded = (jb + 2 * ib) * E * h * 2
+    t_hbm, t_mfma = once / HBM_PEAK, 2 * E * h * h / BF16_MFMA_PEAK
+    for name in fns:
+        med = statistics.median(r[0] for r in res[name])
+        mn = min(r[1] for r in res[name])
+        extra = ""
+        if name == "wgrad_bf16":
+            extra = (f"  loads {loaded / 1e9:.2f} GB ({loaded / (med * 1e-6) / 1e12:.2f} TB/s), operands once "
+                     f"{once / 1e9:.2f} GB: HBM roof {t_hbm * 1e6:.1f} us ({t_hbm / (med * 1e-6):.1%}), "
+                     f"MFMA roof {t_mfma * 1e6:.1f} us ({t_mfma / (med * 1e-6):.1%})")
+        print(f"{name:18s} median {med:8.1f} us  min {mn:8.1f} us{extra}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--mols", type=int, default=4096)
@@ -35,6 +87,8 @@ def main():
     p.add_argument("--abl", default="", help="NT_LIB=diag: comma list of NT_FK_ABL ablations of fk_fused")
     a = p.parse_args()
     G = make_batch(a.kind, a.mols, seed=0).collate("nodes").to("cuda")
+    if a.only == "wgrad_bf16":  # bf16 operands of its own; none of the fp32 set-up below
+        return wgrad_bf16(G, a.h, a.rounds)
     V, E, h = G.num_nodes, G.num_edges, a.h
     lay = G._nt_layout
     gen = torch.Generator(device="cuda").manual_seed(0)
