@@ -70,3 +70,16 @@ def test_python_gate_tile_rows_and_image_size():
     assert not K.fused_supported(10, 20, 8200, torch.bfloat16)
     assert lib.nt_dmpnn_fused_tile_rows(1024, BF16, RELU, SUM, RELU) == 64
     assert lib.nt_dmpnn_packed_weight_bytes(1024, BF16) == 32 * 64 * 64 * 16
+
+
+def test_fp32_wide_tile_rows_and_image_size():
+    """fp32 above hidden 384 (more than 24 column tiles): 64-row tiles for every layer, relu / sum
+    included; the packed image holds the fk image of a width that fills neither its last column tile
+    nor its last k-step (256-byte header + ks x nt fragment blocks of two 1 KiB parts)."""
+    lib = _lib()
+    for h in (388, 516, 8192):
+        assert lib.nt_dmpnn_fused_tile_rows(h, F32, RELU, SUM, RELU) == 64, h
+    assert lib.nt_dmpnn_fused_tile_rows(384, F32, RELU, SUM, RELU) == 128
+    for h in (516, 1028):
+        ks, nt = (h + 31) // 32, (h + 15) // 16
+        assert lib.nt_dmpnn_packed_weight_bytes(h, F32) >= 256 + ks * nt * 2048, h
