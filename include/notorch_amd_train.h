@@ -44,6 +44,51 @@ NT_API int nt_embed_bag_backward(const void* dX, int64_t ld_dx, int64_t n_dx, co
                                  const int32_t* perm, int dx_dtype, int out_dtype, void* out, void* workspace,
                                  int64_t workspace_bytes, void* stream);
 
+/*
+ * Mixed precision (an fp32 ChempropBlock under torch.autocast(dtype=bfloat16)): the boundary between
+ * fp32 leaves and the bf16 storage kernels, with the conversion inside the kernel that consumes the
+ * data.  Every rounding is round-to-nearest-even, once per stored element.  The three entry points
+ * accept the hidden sizes of the bf16 layer kernel (h <= 512, or h % 8 == 0 and h <= 8192; else
+ * NT_EUNSUPPORTED with the rule in the message) and validate on the host before any device call.
+ */
+
+/*
+ * The bf16 weight images of nlayers (1..16) separate h x h weights in ONE launch: W, Wp, WpT, b and
+ * b16 are HOST arrays of nlayers device pointers.  W[l]: row-major h x h in src_dtype (NT_F32 or
+ * NT_BF16; else NT_EUNSUPPORTED).  Wp[l] (16-byte aligned, nt_dmpnn_packed_weight_bytes(h, NT_BF16)
+ * bytes) receives the image nt_dmpnn_pack_weight(NT_BF16) writes for W[l] rounded to bf16.  WpT may be
+ * NULL; else WpT[l] receives the image of W[l]^T (the backward's dA = G W), read from W[l] directly.
+ * b and b16 may both be NULL; else b[l] is NULL (a layer without a bias) or h elements in src_dtype
+ * whose bf16 copy goes to b16[l].  Same bytes as nt_dmpnn_pack_weight of the bf16 copy of W[l] and of
+ * W[l]^T.
+ */
+NT_API int nt_dmpnn_pack_weights_mixed(const void* const* W, int64_t nlayers, int64_t h, int src_dtype,
+                                       void* const* Wp, void* const* WpT, const void* const* b,
+                                       void* const* b16, void* stream);
+
+/*
+ * nt_dmpnn_init for fp32 Xv (V x h) / Xe (E x h) and bf16 outputs: H0[e] = bf16(Xv[src e] + Xe[e]),
+ * added in fp32 and rounded once (not bf16(bf16(xv) + bf16(xe)), what a cast followed by the bf16 init
+ * gives); S (may be NULL: H0 only) = reduce over dst of act(H0) with the arithmetic of the bf16 init,
+ * i.e. the bits of nt_segment_reduce over that H0.  seg_ptr / perm: the dst CSR (needed with S).
+ * Rows of whole 16-byte pieces (h % 8 == 0, 16-byte aligned pointers) move as vectors, others by element.
+ */
+NT_API int nt_dmpnn_init_mixed(const void* Xv, const void* Xe, const int64_t* src, const int32_t* seg_ptr,
+                               const int32_t* perm, int64_t V, int64_t E, int64_t h, int act,
+                               float act_alpha, int reduce, void* H0, void* S, void* stream);
+
+/*
+ * nt_dmpnn_init_embed for fp32 tables and bf16 outputs: both bags summed in fp32 in ascending j, added
+ * in fp32, rounded once.  Bit-identical to nt_embed_bag (NT_F32) twice followed by nt_dmpnn_init_mixed,
+ * with Xv / Xe never written.  An index outside its table contributes nothing.
+ */
+NT_API int nt_dmpnn_init_embed_mixed(const void* node_table, int64_t num_node_types,
+                                     const int64_t* node_types, int64_t kv, const void* edge_table,
+                                     int64_t num_edge_types, const int64_t* edge_types, int64_t ke,
+                                     const int64_t* src, const int32_t* seg_ptr, const int32_t* perm,
+                                     int64_t V, int64_t E, int64_t h, int act, float act_alpha,
+                                     int reduce, void* H0, void* S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

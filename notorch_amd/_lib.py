@@ -160,6 +160,16 @@ EXT_SIGNATURES: dict[str, tuple] = {
         _c_int,
         [_vp, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_i64, _vp],
     ),
+    # mixed precision (fp32 leaves, bf16 storage kernels): csrc/mixed.hip
+    "nt_dmpnn_pack_weights_mixed": (_c_int, [_vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    "nt_dmpnn_init_mixed": (
+        _c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f32, _c_int, _vp, _vp, _vp],
+    ),
+    "nt_dmpnn_init_embed_mixed": (
+        _c_int,
+        [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64,
+         _c_int, _c_f32, _c_int, _vp, _vp, _vp],
+    ),
 }
 
 

@@ -46,6 +46,9 @@ __all__ = [
     "segment_arg",
     "dmpnn_edge_backward_arg",
     "gather_rows_arg",
+    "pack_weights_mixed",
+    "dmpnn_init_mixed",
+    "dmpnn_init_embed_mixed",
 ]
 
 
@@ -497,6 +500,150 @@ def pack_weights_fk_multi(Ws: Sequence[Tensor], with_t: bool = False) -> tuple[l
          arr(*[t.data_ptr() for t in imgs]), None if imgsT is None else arr(*[t.data_ptr() for t in imgsT]),
          _stream(dev))
     return imgs, imgsT
+
+
+# ------------------------------------------------------------------------------------ mixed precision
+def bf16_h_supported(h: int) -> bool:
+    """Hidden sizes of the bf16 storage path (NT_BF16_H_RULE): h <= 512, or h % 8 == 0 up to 8192."""
+    return h >= 1 and (h <= 512 or (h % 8 == 0 and h <= 8192))
+
+
+def pack_weights_mixed(Ws: Sequence[Tensor], biases: Sequence[Tensor | None] | None = None,
+                       with_t: bool = False) -> tuple[list[Tensor], list[Tensor] | None, list[Tensor | None]]:
+    """The bf16 fragment images of up to 16 separate h x h weights of one dtype (fp32 master weights, or
+    bf16), with ``with_t`` of their transposes (the backward's dA image), and the bf16 copies of the
+    given biases (same dtype as the weights; None entries stay None), in one launch
+    (nt_dmpnn_pack_weights_mixed).  Bytes equal pack_weights(W.to(bfloat16)),
+    pack_weights(W.t().contiguous().to(bfloat16)) and b.to(bfloat16).
+    Returns (images, transpose images or None, bf16 biases)."""
+    if not Ws:
+        return [], ([] if with_t else None), []
+    if biases is None:
+        biases = [None] * len(Ws)
+    dev = _require_device(*Ws, *biases)
+    h = Ws[0].shape[0]
+    dtype = Ws[0].dtype
+    code = _require_feat("weight", Ws[0])
+    if len(Ws) > 16:
+        raise ValueError("pack_weights_mixed: at most 16 weights per call")
+    if len(biases) != len(Ws):
+        raise ValueError("pack_weights_mixed: one bias (or None) per weight")
+    if not bf16_h_supported(h):
+        raise ValueError(f"pack_weights_mixed: the bf16 path needs h <= 512, or h % 8 == 0 and h <= 8192; got {h}")
+    for W in Ws:
+        _require_feat("weight", W, dtype)
+        if W.shape != (h, h):
+            raise ValueError("pack_weights_mixed: h x h weights of one hidden size")
+    for b in biases:
+        if b is not None:
+            _require_feat("bias", b, dtype)
+            if b.shape != (h,):
+                raise ValueError("pack_weights_mixed: a bias has h elements")
+    n = packed_weight_numel(h, torch.bfloat16)
+    imgs = [torch.empty(n, dtype=torch.float32, device=dev) for _ in Ws]
+    imgsT = [torch.empty(n, dtype=torch.float32, device=dev) for _ in Ws] if with_t else None
+    b16 = [None if b is None else torch.empty(h, dtype=torch.bfloat16, device=dev) for b in biases]
+    arr = ctypes.c_void_p * len(Ws)
+    any_b = any(b is not None for b in biases)
+    _run(dev, _lib.load().nt_dmpnn_pack_weights_mixed, arr(*[W.data_ptr() for W in Ws]), len(Ws), h, code,
+         arr(*[t.data_ptr() for t in imgs]), None if imgsT is None else arr(*[t.data_ptr() for t in imgsT]),
+         arr(*[_ptr(b) for b in biases]) if any_b else None, arr(*[_ptr(t) for t in b16]) if any_b else None,
+         _stream(dev))
+    return imgs, imgsT, b16
+
+
+def _require_dst_csr(seg_ptr: Tensor | None, perm: Tensor | None, V: int, E: int) -> None:
+    if (seg_ptr is None) != (perm is None):
+        raise ValueError("the dst CSR needs both seg_ptr and perm")
+    if seg_ptr is None:
+        return
+    if seg_ptr.dtype != torch.int32 or seg_ptr.numel() != V + 1 or not seg_ptr.is_contiguous():
+        raise ValueError("seg_ptr must be contiguous int32 of length V + 1")
+    if perm.dtype != torch.int32 or perm.numel() != E or not perm.is_contiguous():
+        raise ValueError("perm must be contiguous int32 with one entry per edge")
+
+
+def dmpnn_init_mixed(
+    Xv: Tensor,
+    Xe: Tensor,
+    src: Tensor,
+    seg_ptr: Tensor | None = None,
+    perm: Tensor | None = None,
+    *,
+    act: tuple[int, float] = (_lib.NT_ACT_RELU, 0.0),
+    reduce: str = "sum",
+) -> tuple[Tensor, Tensor | None]:
+    """dmpnn_init from fp32 Xv / Xe to bf16 outputs (nt_dmpnn_init_mixed): H0 = bf16(Xv[src] + Xe), added
+    in fp32 and rounded once, optionally fused with S = scatter(act(H0), dst) (needs the dst CSR;
+    the bits of segment_reduce over that H0).  Rows of whole 16-byte pieces (h % 8 == 0, which the
+    allocator's alignment then guarantees) move as vectors, other rows by element."""
+    dev = _require_device(Xv, Xe, src, seg_ptr, perm)
+    _require_f32("node_feats", Xv)
+    _require_f32("edge_feats", Xe)
+    _require_i64("src", src)
+    if Xv.dim() != 2 or Xe.dim() != 2 or Xv.shape[1] != Xe.shape[1]:
+        raise RuntimeError(
+            f"node_feats {tuple(Xv.shape)} and edge_feats {tuple(Xe.shape)} must be V x h and E x h"
+        )
+    V, h = Xv.shape
+    E = Xe.shape[0]
+    if src.numel() != E:
+        raise ValueError("src must have one entry per edge")
+    if not bf16_h_supported(h):
+        raise ValueError(f"dmpnn_init_mixed: the bf16 path needs h <= 512, or h % 8 == 0 and h <= 8192; got {h}")
+    _require_dst_csr(seg_ptr, perm, V, E)
+    H0 = torch.empty(E, h, dtype=torch.bfloat16, device=dev)
+    S = None if seg_ptr is None else torch.empty(V, h, dtype=torch.bfloat16, device=dev)
+    _run(dev, _lib.load().nt_dmpnn_init_mixed,
+         _ptr(Xv), _ptr(Xe), _ptr(src), _ptr(seg_ptr), _ptr(perm), V, E, h, act[0], act[1],
+         reduce_code(reduce), _ptr(H0), _ptr(S), _stream(dev))
+    return H0, S
+
+
+def dmpnn_init_embed_mixed(
+    node_table: Tensor,
+    node_types: Tensor,
+    edge_table: Tensor,
+    edge_types: Tensor,
+    src: Tensor,
+    seg_ptr: Tensor | None = None,
+    perm: Tensor | None = None,
+    *,
+    act: tuple[int, float] = (_lib.NT_ACT_RELU, 0.0),
+    reduce: str = "sum",
+    validate: bool = True,
+) -> tuple[Tensor, Tensor | None]:
+    """dmpnn_init_embed from fp32 tables to bf16 outputs (nt_dmpnn_init_embed_mixed): the bits of
+    embed_bag (fp32) twice followed by dmpnn_init_mixed, with Xv / Xe never written."""
+    dev = _require_device(node_table, node_types, edge_table, edge_types, src, seg_ptr, perm)
+    _require_f32("node_table", node_table)
+    _require_f32("edge_table", edge_table)
+    if node_table.dim() != 2 or edge_table.dim() != 2 or node_table.shape[1] != edge_table.shape[1]:
+        raise RuntimeError("node and edge embedding tables must share the hidden dimension")
+    if validate:
+        _check_types("node_types", node_types, node_table.shape[0])
+        _check_types("edge_types", edge_types, edge_table.shape[0])
+    else:
+        _require_i64("node_types", node_types)
+        _require_i64("edge_types", edge_types)
+        if node_types.dim() != 2 or edge_types.dim() != 2:
+            raise ValueError("type indices must be n x k")
+    _require_i64("src", src)
+    V, kv = node_types.shape
+    E, ke = edge_types.shape
+    h = node_table.shape[1]
+    if src.numel() != E:
+        raise ValueError("src must have one entry per edge")
+    if not bf16_h_supported(h):
+        raise ValueError(f"dmpnn_init_embed_mixed: the bf16 path needs h <= 512, or h % 8 == 0 and h <= 8192; got {h}")
+    _require_dst_csr(seg_ptr, perm, V, E)
+    H0 = torch.empty(E, h, dtype=torch.bfloat16, device=dev)
+    S = None if seg_ptr is None else torch.empty(V, h, dtype=torch.bfloat16, device=dev)
+    _run(dev, _lib.load().nt_dmpnn_init_embed_mixed,
+         _ptr(node_table), node_table.shape[0], _ptr(node_types), kv, _ptr(edge_table),
+         edge_table.shape[0], _ptr(edge_types), ke, _ptr(src), _ptr(seg_ptr), _ptr(perm), V, E, h,
+         act[0], act[1], reduce_code(reduce), _ptr(H0), _ptr(S), _stream(dev))
+    return H0, S
 
 
 def dmpnn_update(

@@ -21,6 +21,12 @@ bf16 features (BASELINE config 3) run the same d + 1 launch sequence on the bf16
 kernel code, or layers that differ in activation / dropout, run layer by layer
 (block_forward_layerwise).
 
+Under bf16 autocast (autocast_bf16; block_forward(..., bf16_compute=True)) an fp32 block runs that bf16
+sequence on fp32 leaves: nt_dmpnn_init_mixed / nt_dmpnn_init_embed_mixed read the fp32 features or
+tables (one rounding of the fp32 sum), one nt_dmpnn_pack_weights_mixed launch writes the bf16 images of
+W, W^T (training) and the bf16 biases of every layer (pack_layer_weights_bf16), and block_backward
+returns dW / db in the parameter's dtype (the weight-gradient kernel's fp32 result for an fp32 weight).
+
 Backward (training): the forward keeps (H_l, S_l) of every layer; per layer,
 last to first (csrc/backward.hip, csrc/wgrad.hip):
 
@@ -37,6 +43,7 @@ then dXe = G, dXv = scatter_sum(G, src).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import threading
 import weakref
@@ -303,7 +310,26 @@ def _fused_enabled() -> bool:
 # repack after every step.
 # (Keyed by id() with a weakref check: tensors cannot be WeakKeyDictionary keys because their
 # __eq__ is element-wise.)
-_PACKED: dict[int, tuple] = {}
+_PACKED: dict[int, list] = {}
+# entry slots: weakref, key, the image of the parameter's own dtype (fp32: fk image), that of W^T,
+# and for an fp32 parameter under bf16 autocast the bf16 image, the bf16 image of W^T and the bf16
+# copy of its layer's bias as (weakref, key, copy): side by side, all dropped when the key changes
+_FK, _FKT, _BF, _BFT, _BIAS = 2, 3, 4, 5, 6
+
+
+def _param_key(W: Tensor) -> tuple:
+    return (W.data_ptr(), W._version, tuple(W.shape), W.device)
+
+
+def _entry(W: Tensor) -> list:
+    """The cache entry of parameter W, emptied if W changed since it was made."""
+    wid = id(W)
+    key = _param_key(W)
+    hit = _PACKED.get(wid)
+    if hit is None or hit[0]() is not W or hit[1] != key:
+        ref = weakref.ref(W, lambda _r, wid=wid: _PACKED.pop(wid, None))
+        hit = _PACKED[wid] = [ref, key, None, None, None, None, None]
+    return hit
 
 
 def _multi_packable(W: Tensor) -> bool:
@@ -319,12 +345,11 @@ def pack_layer_weights(weights: Sequence[Tensor], with_t: bool = False) -> list[
     out: list = [None] * len(weights)
     stale = []  # (index, W) needing a pack
     for i, W in enumerate(weights):
-        key = (W.data_ptr(), W._version, tuple(W.shape), W.device)
-        hit = _PACKED.get(id(W))
-        if hit is None or hit[0]() is not W or hit[1] != key or (with_t and hit[3] is None):
+        hit = _entry(W)
+        if hit[_FK] is None or (with_t and hit[_FKT] is None):
             stale.append((i, W))
         else:
-            out[i] = hit[2]
+            out[i] = hit[_FK]
     multi = [(i, W) for i, W in stale if _multi_packable(W)]
     uniq: dict = {}
     for i, W in multi:
@@ -341,25 +366,96 @@ def pack_layer_weights(weights: Sequence[Tensor], with_t: bool = False) -> list[
     for i, W in stale:
         if not _multi_packable(W):
             _remember(W, K.pack_weights(W.detach()), None)
-        out[i] = _PACKED[id(W)][2]
+        out[i] = _PACKED[id(W)][_FK]
     return out
 
 
 def _remember(W: Tensor, Wp: Tensor, WpT: Optional[Tensor]) -> None:
-    key = (W.data_ptr(), W._version, tuple(W.shape), W.device)
-    wid = id(W)
-    ref = weakref.ref(W, lambda _r, wid=wid: _PACKED.pop(wid, None))
-    _PACKED[wid] = (ref, key, Wp, WpT)
+    hit = _entry(W)
+    hit[_FK], hit[_FKT] = Wp, WpT
 
 
-def packed_transpose(W: Tensor) -> Tensor:
+def _bias_copy(hit: list, b: Tensor) -> Optional[Tensor]:
+    """The cached bf16 copy of fp32 bias b in its weight's entry, if b is unchanged since."""
+    c = hit[_BIAS]
+    if c is not None and c[0]() is b and c[1] == _param_key(b):
+        return c[2]
+    return None
+
+
+def pack_layer_weights_bf16(weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]],
+                            with_t: bool = False) -> tuple[list[Tensor], list[Optional[Tensor]]]:
+    """bf16 compute of a block whose parameters may be fp32 master weights (bf16 autocast): per layer
+    the bf16 fragment image and the bf16 bias.  An fp32 weight's image, with_t (a training forward)
+    the image of its W^T for the backward's dA, and the bf16 copy of its fp32 bias come from ONE
+    nt_dmpnn_pack_weights_mixed launch for all stale layers (chunks of 16 distinct weights; a shared
+    layer is packed once) and are cached beside the parameter's fp32 image.  A bf16 parameter is
+    used as it is (the bf16 path's own packing)."""
+    d = len(weights)
+    stale: dict = {}  # id(W) -> (W, fp32 bias or None)
+    for W, b in zip(weights, biases):
+        if W.dtype != torch.float32:
+            continue
+        hit = _entry(W)
+        b32 = b if (b is not None and b.dtype == torch.float32) else None
+        if (hit[_BF] is None or (with_t and hit[_BFT] is None)
+                or (b32 is not None and _bias_copy(hit, b32) is None)):
+            stale.setdefault(id(W), (W, b32))
+    groups: dict = {}
+    for W, b32 in stale.values():
+        groups.setdefault((W.shape[0], W.device), []).append((W, b32))
+    for ws in groups.values():
+        for c in range(0, len(ws), 16):
+            chunk = ws[c:c + 16]
+            imgs, imgsT, b16 = K.pack_weights_mixed([W.detach().contiguous() for W, _ in chunk],
+                                                    [None if b is None else b.detach().contiguous()
+                                                     for _, b in chunk], with_t=with_t)
+            for j, (W, b32) in enumerate(chunk):
+                hit = _entry(W)
+                hit[_BF] = imgs[j]
+                if imgsT is not None:
+                    hit[_BFT] = imgsT[j]
+                if b32 is not None:
+                    hit[_BIAS] = (weakref.ref(b32), _param_key(b32), b16[j])
+    Wps: list = [None] * d
+    bs: list = [None] * d
+    for i, (W, b) in enumerate(zip(weights, biases)):
+        if W.dtype == torch.float32:
+            hit = _entry(W)
+            Wps[i] = hit[_BF]
+        else:
+            Wps[i] = pack_layer_weights([W])[0]
+        if b is None:
+            continue
+        if b.dtype == torch.bfloat16:
+            bs[i] = b.detach()
+        else:  # the copy packed with its weight; a bias that is not its weight's own is cast by torch
+            c = _bias_copy(_entry(W), b) if W.dtype == torch.float32 else None
+            bs[i] = c if c is not None else b.detach().to(torch.bfloat16)
+    return Wps, bs
+
+
+def packed_transpose(W: Tensor, bf16: bool = False) -> Tensor:
     """The fk image of W^T (the backward's dA = G W): the one the training forward packed beside W's
-    if W is unchanged since, else packed now."""
-    key = (W.data_ptr(), W._version, tuple(W.shape), W.device)
-    hit = _PACKED.get(id(W))
-    if hit is not None and hit[0]() is W and hit[1] == key and hit[3] is not None:
-        return hit[3]
+    if W is unchanged since, else packed now.  bf16 (an fp32 master weight under bf16 compute): the
+    bf16 image of W^T, likewise."""
+    hit = _entry(W)
+    if bf16:
+        if hit[_BFT] is None:
+            imgs, imgsT, _ = K.pack_weights_mixed([W.detach().contiguous()], None, with_t=True)
+            hit[_BF], hit[_BFT] = imgs[0], imgsT[0]
+        return hit[_BFT]
+    if hit[_FKT] is not None:
+        return hit[_FKT]
     return K.pack_weights(W.detach().t().contiguous(), fk_only=True)
+
+
+def autocast_bf16(device) -> bool:
+    """bf16 autocast is active for this device: inside torch.autocast("cuda", dtype=torch.bfloat16) and
+    not inside a nested autocast(enabled=False) or an autocast of another dtype."""
+    if torch.device(device).type != "cuda":
+        return False
+    return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
 
 
 def block_forward(
@@ -375,13 +471,28 @@ def block_forward(
     residual: bool,
     keep_states: bool = False,
     drop: Optional[tuple[float, int]] = None,
+    bf16_compute: bool = False,
 ) -> tuple[Tensor, Tensor, list[tuple[Tensor, Tensor]]]:
     """Run the kernel sequence; returns (node, H_d, states) with states = [(H_l, S_l, amax_l)] for
     l = 0..d-1 (each layer's input hidden state, its aggregation and the fp32 split bounds (max|H_l|,
     max|S_l|) on the device, or an empty tensor) if keep_states, else [].
     drop = (p, seed): training-mode dropout of every layer update (layer l draws from
-    dropout_offset(l, E, h))."""
+    dropout_offset(l, E, h)).
+    bf16_compute (the block under bf16 autocast): fp32 Xv / Xe enter through nt_dmpnn_init_mixed (one
+    rounding of the fp32 sum), fp32 weights and biases through nt_dmpnn_pack_weights_mixed
+    (_layers_forward), and the bf16 kernel sequence runs unchanged; outputs and states are bf16.  Xv and
+    Xe share one dtype here (ChempropBlock casts the odd one of an fp32 / bf16 pair)."""
     V = Xv.shape[0]
+    if bf16_compute and Xv.dtype == torch.float32:
+        chunks = dst_chunks(lay)
+        if len(weights) == 0 or chunks is not None:  # as the bf16 path: H0, then the (chunked) reduce
+            H, S = K.dmpnn_init_mixed(Xv, Xe, src)
+            if len(weights):
+                S = _aggregate(H, lay.dst_ptr, lay.dst_perm, V, reduce, act, chunks)
+        else:
+            H, S = K.dmpnn_init_mixed(Xv, Xe, src, lay.dst_ptr, lay.dst_perm, act=act, reduce=reduce)
+        return _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual, keep_states,
+                               drop)
     amax = _amax_buffer(len(weights), Xv, reuse=not keep_states)
     a0 = None if amax is None else amax[0]
     if len(weights) == 0:
@@ -492,10 +603,17 @@ def block_forward_embedded(
     reduce: str,
     residual: bool,
     validate: bool = True,
+    bf16_compute: bool = False,
 ) -> tuple[Tensor, Tensor]:
     """block_forward with GraphEmbedding fused into the initial gather (nt_dmpnn_init_embed):
-    Xv / Xe are never materialised.  Returns (node, H_d)."""
+    Xv / Xe are never materialised.  Returns (node, H_d).  bf16_compute (bf16 autocast): fp32 tables
+    enter through nt_dmpnn_init_embed_mixed and the bf16 kernel sequence runs (bf16 outputs)."""
     V = node_types.shape[0]
+    if bf16_compute and node_table.dtype == torch.float32:
+        H, S = embed_init_mixed(node_table, node_types, edge_table, edge_types, src, lay, len(weights), act,
+                                reduce, validate)
+        node, H, _ = _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual, False)
+        return node, H
     if len(weights) == 0:
         H, _ = K.dmpnn_init_embed(node_table, node_types, edge_table, edge_types, src, validate=validate)
         node, H, _ = _layers_forward(H, None, V, src, rev, lay, weights, biases, act, reduce, residual, False)
@@ -515,6 +633,20 @@ def block_forward_embedded(
     return node, H
 
 
+def embed_init_mixed(node_table, node_types, edge_table, edge_types, src, lay, nlayers, act, reduce, validate):
+    """(H0, S) in bf16 from fp32 embedding tables (nt_dmpnn_init_embed_mixed); S is None for depth 0.
+    Routed as block_forward routes fp32 features: on a graph with long segments (dst_chunks) H0 alone,
+    then the chunked reduce, so the fused and the unfused embedding sum S in the same order."""
+    chunks = dst_chunks(lay)
+    if nlayers == 0 or chunks is not None:
+        H, S = K.dmpnn_init_embed_mixed(node_table, node_types, edge_table, edge_types, src, validate=validate)
+        if nlayers:
+            S = _aggregate(H, lay.dst_ptr, lay.dst_perm, node_types.shape[0], reduce, act, chunks)
+        return H, S
+    return K.dmpnn_init_embed_mixed(node_table, node_types, edge_table, edge_types, src, lay.dst_ptr,
+                                    lay.dst_perm, act=act, reduce=reduce, validate=validate)
+
+
 def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual, keep_states, drop=None,
                     amax=None):
     """The d layers + final node scatter, from H0 and layer 0's aggregation S.  With dropout the
@@ -527,8 +659,15 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
         node = _aggregate(H, lay.dst_ptr, lay.dst_perm, V, reduce, _IDENTITY, chunks)
         return node, H, []
     # a training forward (states kept for the kernel backward) packs the dA images of W^T alongside
-    Wps = pack_layer_weights(weights, with_t=keep_states and H.dtype == torch.float32)
     E, h = H.shape
+    if H.dtype == torch.bfloat16 and any(p is not None and p.dtype == torch.float32
+                                         for p in (*weights, *biases)):
+        # bf16 compute on fp32 master parameters (bf16 autocast): their bf16 images and bias copies, and
+        # in a training forward whose backward runs dA on the bf16 layer kernel the W^T images, in one launch
+        Wps, biases = pack_layer_weights_bf16(
+            weights, biases, with_t=keep_states and K.fused_supported(V, E, h, torch.bfloat16))
+    else:
+        Wps = pack_layer_weights(weights, with_t=keep_states and H.dtype == torch.float32)
     fp32 = H.dtype == torch.float32
     if fp32 and amax is None:
         amax = _amax_buffer(d, H)
@@ -854,12 +993,23 @@ def backward_layout(lay: DeviceLayout, src: Tensor, rev: Tensor, V: int, E: int)
     return bwd[2:]
 
 
-def _weight_grad(G: Tensor, A: Tensor) -> Tensor:
+def _weight_grad(G: Tensor, A: Tensor, out_dtype: Optional[torch.dtype] = None) -> Tensor:
     """dW = G^T A (h x h, reduction over all E edges).  A single GEMM has only (h/32)(h/64) output
     tiles, far too few for 256 CUs, so the edge dimension is split k ways into a batched GEMM
-    whose k partial products are then summed (split-K)."""
+    whose k partial products are then summed (split-K).  out_dtype float32 for bf16 G (an fp32 master
+    weight under bf16 compute): the library's fp32 accumulators, not rounded to bf16."""
     E, h = G.shape
     k = min(64, E // 2048)
+    if out_dtype is not None and out_dtype != G.dtype:
+        if k < 2:
+            return torch.mm(G.t(), A, out_dtype=out_dtype)
+        rows = E // k
+        Eb = rows * k
+        dW = torch.bmm(G[:Eb].view(k, rows, h).transpose(1, 2), A[:Eb].view(k, rows, h),
+                       out_dtype=out_dtype).sum(0)
+        if Eb < E:
+            dW += torch.mm(G[Eb:].t(), A[Eb:], out_dtype=out_dtype)
+        return dW
     if k < 2:
         return torch.mm(G.t(), A)
     rows = E // k
@@ -908,6 +1058,8 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
     for l in range(d - 1, -1, -1):
         H_l, S_l, am_l = states[l]
         W = weights[l].detach()
+        # an fp32 master weight under bf16 compute (bf16 autocast): G and the states are bf16
+        master = weights[l] if (gdtype == torch.bfloat16 and W.dtype == torch.float32) else None
         # dropout: the update's gradient is keep * G / (1 - p); the residual path keeps G
         Gu = G if drop is None else K.dropout_residual(G, drop[0], drop[1], dropout_offset(l, E, h))
         Gu = Gu.contiguous()
@@ -936,11 +1088,12 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
                                            amax_G=None if am is None else gmax[1:2], amax_HS=am)
         elif bf16_wgrad:  # A rounded to bf16 in the kernel as the forward's message; fp32 partials
             dW32, db32 = K.weight_grad(Gu, H_l.contiguous(), S_l.contiguous(), src, rev, act=act)
-            dWs[l], dbs[l] = dW32.to(Gu.dtype), db32.to(Gu.dtype)
+            # in the parameter's dtype: an fp32 master weight (bf16 autocast) keeps the fp32 result
+            dWs[l], dbs[l] = dW32.to(W.dtype), db32.to(W.dtype)
         else:
             A = K.dmpnn_message(H_l, S_l, src, rev, act=act)
-            dWs[l] = _weight_grad(Gu, A)
-            dbs[l] = Gu.sum(0)
+            dWs[l] = _weight_grad(Gu, A, W.dtype)
+            dbs[l] = Gu.sum(0) if master is None else Gu.sum(0, dtype=W.dtype)
             del A
         dap = dA_plan(lay, src, V, E, src_ptr, src_perm) if (fk_dense and _FUSED_DA) else None
         if dap is not None:
@@ -959,9 +1112,11 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
             if fk_dense:
                 dA = K.dense_matmul(Gu, packed_transpose(weights[l]), amax=gmax)
             elif bf16_da and os.environ.get("NT_BF16_DA", "kernel") == "kernel":  # the bf16 layer kernel
-                dA = K.dense_matmul(Gu, K.pack_weights(W.t().contiguous()))  # without gathers
+                # without gathers; an fp32 master weight: the W^T image the forward's pack launch wrote
+                dA = K.dense_matmul(Gu, K.pack_weights(W.t().contiguous()) if master is None
+                                    else packed_transpose(master, bf16=True))
             else:
-                dA = torch.mm(Gu, W)
+                dA = torch.mm(Gu, W if master is None else W.to(Gu.dtype))
             dS = K.segment_reduce(dA, src_ptr, src_perm, V, reduce="sum", act=_IDENTITY)
         del Gu
         gmax_cur = gbuf[l - 1] if fp32 and l > 0 else None
@@ -980,23 +1135,32 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
 class ChempropBlockFunction(torch.autograd.Function):
     """Kernel forward; kernel backward (block_backward: gather / scatter / element-wise HIP kernels and
     the MFMA dA / dW kernels) for every reduce in fp32 and bf16 storage; NT_BWD=torch selects the
-    recompute-in-torch-device-ops backward (an A/B reference only)."""
+    recompute-in-torch-device-ops backward (an A/B reference only).
+    bf16_compute (the block under bf16 autocast): fp32 inputs and parameters are rounded once to bf16
+    inside the kernels that read them, the bf16 kernel sequence runs, and every leaf's gradient comes
+    back in the leaf's dtype: an fp32 weight or bias gets the weight-gradient kernel's fp32 dW / db
+    as they are, fp32 Xv / Xe the bf16 gradient widened.  The NT_BWD=torch recompute then runs on the
+    rounded copies and widens its results."""
+
+    NFIX = 12  # inputs ahead of the layer parameters
 
     @staticmethod
-    def forward(ctx, Xv, Xe, edge_index, rev, lay, act_mod, act, reduce, residual, nlayers, drop, *params):
+    def forward(ctx, Xv, Xe, edge_index, rev, lay, act_mod, act, reduce, residual, nlayers, drop, bf16_compute,
+                *params):
         weights = list(params[:nlayers])
         biases = list(params[nlayers:])
         src = edge_index[0].contiguous()
         kernel_bwd = (reduce in ("sum", "mean", "max", "min") and Xv.dtype in (torch.float32, torch.bfloat16)
                       and os.environ.get("NT_BWD", "kernel") != "torch")
         node, H, states = block_forward(Xv, Xe, src, rev, lay, weights, biases, act, reduce, residual,
-                                        keep_states=kernel_bwd, drop=drop)
+                                        keep_states=kernel_bwd, drop=drop, bf16_compute=bf16_compute)
         flat = [t for hs in states for t in hs]
         if kernel_bwd and reduce in ("max", "min"):
             flat.append(H)  # the final node scatter's arg is taken over H_d
         ctx.save_for_backward(Xv, Xe, edge_index, rev,
                               *[p if p is not None else torch.empty(0) for p in params], *flat)
         ctx.cfg = (act_mod, act, reduce, residual, nlayers, [p is None for p in params], lay, kernel_bwd, drop)
+        ctx.bf16_compute = bf16_compute
         # an output the loss does not use arrives as None instead of an E x h zero tensor: the backward
         # then writes G = dnode[dst] whole (no zero fill, no zero base read by the gather)
         ctx.set_materialize_grads(False)
@@ -1009,8 +1173,9 @@ class ChempropBlockFunction(torch.autograd.Function):
         nparams = len(is_none)
         params = [None if n else p for p, n in zip(rest[:nparams], is_none)]
         need = ctx.needs_input_grad
+        nfix = ChempropBlockFunction.NFIX
         if dnode is None and dH is None:  # set_materialize_grads(False): neither output reached the loss
-            return (None,) * (11 + nparams)
+            return (None,) * (nfix + nparams)
         if kernel_bwd:
             flat = rest[nparams:]
             states = [tuple(flat[3 * i:3 * i + 3]) for i in range(nlayers)]
@@ -1021,18 +1186,22 @@ class ChempropBlockFunction(torch.autograd.Function):
                 dnode, dH, states, params[:nlayers], src, dst, rev, lay, act, reduce, residual,
                 Xv.shape[0], (need[0], need[1]), drop, H_last,
             )
-            res_params = [dW if need[11 + i] else None for i, dW in enumerate(dWs)]
-            res_params += [None if p is None or not need[11 + nlayers + i] else dbs[i]
+            if ctx.bf16_compute:  # fp32 features: the bf16 gradient widened
+                dXv = None if dXv is None else dXv.to(Xv.dtype)
+                dXe = None if dXe is None else dXe.to(Xe.dtype)
+            res_params = [dW if need[nfix + i] else None for i, dW in enumerate(dWs)]
+            res_params += [None if p is None or not need[nfix + nlayers + i] else dbs[i].to(p.dtype)
                            for i, p in enumerate(params[nlayers:])]
-            return (dXv, dXe, None, None, None, None, None, None, None, None, None, *res_params)
-        with torch.enable_grad():
-            Xv_ = Xv.detach().requires_grad_(need[0])
-            Xe_ = Xe.detach().requires_grad_(need[1])
-            ps = [None if p is None else p.detach().requires_grad_(True) for p in params]
+            return (dXv, dXe, *([None] * (nfix - 2)), *res_params)
+        low = torch.bfloat16 if ctx.bf16_compute else None  # the recompute runs on the rounded copies
+        with torch.enable_grad(), (torch.autocast("cuda", enabled=False) if low else contextlib.nullcontext()):
+            Xv_ = Xv.detach().to(low or Xv.dtype).requires_grad_(need[0])
+            Xe_ = Xe.detach().to(low or Xe.dtype).requires_grad_(need[1])
+            ps = [None if p is None else p.detach().to(low or p.dtype).requires_grad_(True) for p in params]
             masks = None
             if drop is not None:
                 E, h = Xe.shape
-                ones = torch.ones_like(Xe)
+                ones = torch.ones_like(Xe_)
                 masks = [K.dropout_residual(ones, drop[0], drop[1], dropout_offset(l, E, h))
                          for l in range(nlayers)]
             node, H = _torch_block(Xv_, Xe_, edge_index, rev, ps[:nlayers], ps[nlayers:], act_mod, reduce,
@@ -1047,7 +1216,10 @@ class ChempropBlockFunction(torch.autograd.Function):
         it = iter(got)
         res_inputs = [next(it) if need[0] else None, next(it) if need[1] else None]
         res_params = [None if p is None else next(it) for p in ps]
-        return (*res_inputs, None, None, None, None, None, None, None, None, None, *res_params)
+        if low is not None:  # each result in its leaf's dtype
+            res_inputs = [None if g is None else g.to(x.dtype) for g, x in zip(res_inputs, (Xv, Xe))]
+            res_params = [None if g is None else g.to(p.dtype) for g, p in zip(res_params, params)]
+        return (*res_inputs, *([None] * (nfix - 2)), *res_params)
 
 
 def _grad_rows(g: Tensor) -> Tensor:
@@ -1083,20 +1255,27 @@ class EmbeddedBlockFunction(torch.autograd.Function):
     down to G = dL/dH0 (dXv is never reduced), then nt_embed_bag_backward twice over G: the edge table
     from (G, edge_types), the node table from (G, node_types) through the src CSR.  A table or parameter
     that needs no gradient gets None and no launch.  NT_BWD=torch: the recompute-in-torch backward of
-    the unfused pair (A/B reference only)."""
+    the unfused pair (A/B reference only).  bf16_compute (bf16 autocast): fp32 tables enter through
+    nt_dmpnn_init_embed_mixed, the bf16 kernels run, fp32 tables receive nt_embed_bag_backward's fp32
+    output and fp32 weights / biases the weight-gradient kernel's fp32 dW / db."""
 
-    NFIX = 14  # inputs ahead of the layer parameters
+    NFIX = 15  # inputs ahead of the layer parameters
 
     @staticmethod
     def forward(ctx, node_table, edge_table, node_types, edge_types, edge_index, rev, lay, act_mod, act, reduce,
-                residual, nlayers, drop, validate, *params):
+                residual, nlayers, drop, validate, bf16_compute, *params):
         weights = list(params[:nlayers])
         biases = list(params[nlayers:])
         src = edge_index[0].contiguous()
         V = node_types.shape[0]
         kernel_bwd = os.environ.get("NT_BWD", "kernel") != "torch"
         Tv, Te = node_table.detach(), edge_table.detach()
-        if nlayers == 0:
+        ctx.bf16_compute = bf16_compute
+        if bf16_compute and Tv.dtype == torch.float32:
+            H, S = embed_init_mixed(Tv, node_types, Te, edge_types, src, lay, nlayers, act, reduce, validate)
+            node, H, states = _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual,
+                                              kernel_bwd, drop)
+        elif nlayers == 0:
             H, _ = K.dmpnn_init_embed(Tv, node_types, Te, edge_types, src, validate=validate)
             node, H, states = _layers_forward(H, None, V, src, rev, lay, weights, biases, act, reduce, residual,
                                               kernel_bwd, drop)
@@ -1148,18 +1327,19 @@ class EmbeddedBlockFunction(torch.autograd.Function):
                 dTv = K.embed_bag_backward(_grad_rows(G), node_types, node_table.shape[0], src_ptr, src_perm,
                                            out_dtype=node_table.dtype)
             res_params = [dW if need[nfix + i] else None for i, dW in enumerate(dWs)]
-            res_params += [None if p is None or not need[nfix + nlayers + i] else dbs[i]
+            res_params += [None if p is None or not need[nfix + nlayers + i] else dbs[i].to(p.dtype)
                            for i, p in enumerate(params[nlayers:])]
             return (dTv, dTe, *([None] * (nfix - 2)), *res_params)
-        with torch.enable_grad():
+        low = torch.bfloat16 if ctx.bf16_compute else None  # the recompute runs on the rounded copies
+        with torch.enable_grad(), (torch.autocast("cuda", enabled=False) if low else contextlib.nullcontext()):
             tv = node_table.detach().requires_grad_(need[0])
             te = edge_table.detach().requires_grad_(need[1])
-            Xv_ = torch.nn.functional.embedding_bag(node_types, tv, mode="sum")
-            Xe_ = torch.nn.functional.embedding_bag(edge_types, te, mode="sum")
-            ps = [None if p is None else p.detach().requires_grad_(True) for p in params]
+            Xv_ = torch.nn.functional.embedding_bag(node_types, tv, mode="sum").to(low or tv.dtype)
+            Xe_ = torch.nn.functional.embedding_bag(edge_types, te, mode="sum").to(low or te.dtype)
+            ps = [None if p is None else p.detach().to(low or p.dtype).requires_grad_(True) for p in params]
             masks = None
             if drop is not None:
-                ones = torch.ones(E, edge_table.shape[1], dtype=edge_table.dtype, device=edge_table.device)
+                ones = torch.ones(E, edge_table.shape[1], dtype=Xe_.dtype, device=edge_table.device)
                 masks = [K.dropout_residual(ones, drop[0], drop[1], dropout_offset(l, E, ones.shape[1]))
                          for l in range(nlayers)]
             node, H = _torch_block(Xv_, Xe_, edge_index, rev, ps[:nlayers], ps[nlayers:], act_mod, reduce,
@@ -1174,6 +1354,8 @@ class EmbeddedBlockFunction(torch.autograd.Function):
         it = iter(got)
         res_tables = [next(it) if need[0] else None, next(it) if need[1] else None]
         res_params = [None if p is None else next(it) for p in ps]
+        if low is not None:  # each result in its leaf's dtype
+            res_params = [None if g is None else g.to(p.dtype) for g, p in zip(res_params, params)]
         return (*res_tables, *([None] * (nfix - 2)), *res_params)
 
 

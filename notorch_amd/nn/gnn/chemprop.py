@@ -18,6 +18,19 @@ Differences by design:
   GELU, SiLU, Tanh and Sigmoid are fused into the kernels; any other module (e.g. ``nn.PReLU``,
   whose parameters train) runs as its own elementwise op between the segment-reduce and update
   kernels (``_engine.block_forward_layerwise``).
+
+Mixed precision.  Inside ``torch.autocast(device_type="cuda", dtype=torch.bfloat16)`` (what Lightning's
+``precision="bf16-mixed"`` wraps the forward in) a ``ChempropBlock`` whose layers share one fused
+activation and dropout behaves as one lower-precision autocast op: every fp32 input and parameter is
+rounded once to bf16 (round-to-nearest-even; bf16 ones are used as they are) inside the kernel that
+reads it, the bf16 kernel path runs, ``node_feats`` / ``edge_feats`` come back in bf16, and each leaf's
+gradient comes back in the leaf's dtype (an fp32 weight or bias receives the weight-gradient
+kernel's fp32 dW / db without a rounding to bf16, fp32 features the bf16 gradient widened).  The
+parameters and the optimizer state stay fp32.  It applies where the bf16 storage path supports the
+hidden size (h <= 512, or h % 8 == 0 up to 8192); elsewhere, and in fp16 autocast, in a nested
+``autocast(enabled=False)``, for the standalone ``ChempropLayer`` and on the layer-by-layer path for
+generic or mixed activations, the block runs exactly as it does outside autocast (fp32 kernels for
+fp32 tensors; mixed dtypes raise).  ``block.to(torch.bfloat16)`` is unchanged.
 """
 from __future__ import annotations
 
@@ -52,8 +65,22 @@ def _dropout(layers: list["ChempropLayer"]):
     return ps.pop(), _engine.draw_dropout_seed()
 
 
+_AUTOCAST_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def autocast_bf16_applies(device, h: int, tensors) -> bool:
+    """The block runs as one lower-precision autocast op: bf16 autocast is active for the device, the
+    bf16 storage path takes this hidden size (h <= 512, or h % 8 == 0 up to 8192), every floating
+    input and parameter is fp32 or bf16 and at least one is fp32 (all bf16 is today's bf16 path)."""
+    if not _engine.autocast_bf16(device) or not K.bf16_h_supported(h):
+        return False
+    dtypes = {t.dtype for t in tensors if t is not None}
+    return dtypes <= set(_AUTOCAST_DTYPES) and torch.float32 in dtypes
+
+
 class ChempropLayer(nn.Module):
-    """One bond-message update (chemprop.py:13-46)."""
+    """One bond-message update (chemprop.py:13-46).  Standalone, it does not take part in autocast:
+    it runs in the dtype of its inputs and parameters."""
 
     def __init__(
         self,
@@ -106,7 +133,7 @@ class ChempropLayer(nn.Module):
                 return H
             _, H = _engine.ChempropBlockFunction.apply(
                 Xv, edge_feats, edge_index, rev_index.contiguous(), lay, self.act, act, self.reduce,
-                False, 1, drop, self.linear.weight, self.linear.bias,
+                False, 1, drop, False, self.linear.weight, self.linear.bias,
             )
             return H
         seg_ptr, perm = self._csr(edge_index, rev_index, V)
@@ -168,12 +195,19 @@ class ChempropBlock(nn.Module):
                 "hidden dimension (chemprop.py:83)"
             )
         layers = self._chemprop_layers()
-        if Xv.dtype != Xe.dtype or any(l.linear.weight.dtype != Xv.dtype for l in layers):
+        codes = [_engine.layer_act(layer.act) for layer in layers]
+        dps = [float(l.update[1].p) if l.training and l.update[1].p > 0 else None for l in layers]
+        uniform = all(c is not None for c in codes) and len(set(codes)) <= 1 and len(set(dps)) <= 1
+        bf16_compute = uniform and autocast_bf16_applies(
+            Xv.device, Xv.shape[1], [Xv, Xe] + [p for l in layers for p in (l.linear.weight, l.linear.bias)])
+        if not bf16_compute and (Xv.dtype != Xe.dtype or any(l.linear.weight.dtype != Xv.dtype for l in layers)):
             # what nn.Linear / the Xv[src] + Xe add would raise on mixed dtypes in the reference
             raise RuntimeError(
                 f"node_feats ({Xv.dtype}), edge_feats ({Xe.dtype}) and the layer weights must share "
                 "one dtype (float32, or bfloat16 after block.to(torch.bfloat16))"
             )
+        if bf16_compute and Xv.dtype != Xe.dtype:  # the rare pair: the fp32 one is cast by torch
+            Xv, Xe = Xv.to(torch.bfloat16), Xe.to(torch.bfloat16)
         residual = bool(layers) and isinstance(self.layers[0], Residual)
         lay = _engine.dst_layout(G)
         Xv = Xv.contiguous()
@@ -184,9 +218,6 @@ class ChempropBlock(nn.Module):
         needs_grad = torch.is_grad_enabled() and (
             Xv.requires_grad or Xe.requires_grad or any(p.requires_grad for p in self.parameters())
         )
-        codes = [_engine.layer_act(layer.act) for layer in layers]
-        dps = [float(l.update[1].p) if l.training and l.update[1].p > 0 else None for l in layers]
-        uniform = all(c is not None for c in codes) and len(set(codes)) <= 1 and len(set(dps)) <= 1
         if not uniform:
             seed = _engine.draw_dropout_seed() if any(p is not None for p in dps) else 0
             drops = [None if p is None else (p, seed) for p in dps]  # disjoint per-layer offsets
@@ -212,11 +243,12 @@ class ChempropBlock(nn.Module):
         if needs_grad:
             node, H = _engine.ChempropBlockFunction.apply(
                 Xv, Xe, G.edge_index, rev, lay, layers[0].act if layers else nn.Identity(), act,
-                self.reduce, residual, len(layers), drop, *weights, *biases,
+                self.reduce, residual, len(layers), drop, bf16_compute, *weights, *biases,
             )
         else:
             src = G.edge_index[0].contiguous()
             node, H, _ = _engine.block_forward(
-                Xv, Xe, src, rev, lay, weights, biases, act, self.reduce, residual, drop=drop
+                Xv, Xe, src, rev, lay, weights, biases, act, self.reduce, residual, drop=drop,
+                bf16_compute=bf16_compute,
             )
         return G.update(node_feats=node, edge_feats=H)

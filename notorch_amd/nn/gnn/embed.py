@@ -22,6 +22,15 @@ never written either).  ``fuse=False`` is the embedding kernels, then the block;
 ``EmbedBagFunction`` followed by ``ChempropBlockFunction``.  Mixed or generic activations go through
 ``block(embedding(G))``.  ``NT_EMBED_BWD=torch`` selects the library path for training instead
 (``nn.EmbeddingBag`` under autograd, then the block; an A/B reference).
+
+Mixed precision.  Under ``torch.autocast(device_type="cuda", dtype=torch.bfloat16)``
+``EmbeddedChempropBlock`` behaves as one lower-precision op like ``ChempropBlock`` (see
+``nn/gnn/chemprop.py``): fp32 tables enter through ``nt_dmpnn_init_embed_mixed`` (both bags summed in
+fp32, added in fp32, one rounding to bf16), the bf16 kernels run, the outputs are bf16, and an fp32
+table receives the fp32 output of ``nt_embed_bag_backward``.  ``fuse=True`` and ``fuse=False`` return the
+same bits.  ``GraphEmbedding`` on its own does not take part in autocast: it returns the dtype of its
+tables (fp32 for fp32 tables, as torch's ``embedding_bag`` under autocast), and the readouts follow
+the dtype of their input.
 """
 from __future__ import annotations
 
@@ -36,7 +45,7 @@ from notorch_amd._lib import NT_ACT_IDENTITY
 from notorch_amd.data.models.graph import types_in_range
 from notorch_amd.data.synth import DEFAULT_NUM_ATOM_TYPES, DEFAULT_NUM_BOND_TYPES
 from notorch_amd.nn.gnn import _engine
-from notorch_amd.nn.gnn.chemprop import ChempropBlock, _dropout
+from notorch_amd.nn.gnn.chemprop import ChempropBlock, _dropout, autocast_bf16_applies
 from notorch_amd.nn.residual import Residual
 
 DEFAULT_HIDDEN_DIM = 256  # notorch/conf.py
@@ -134,7 +143,11 @@ class EmbeddedChempropBlock(nn.Module):
         dps = {float(l.update[1].p) if l.training and l.update[1].p > 0 else None for l in layers}
         if not fusable or any(c is None for c in codes) or len(set(codes)) > 1 or len(dps) > 1:
             return blk(emb(G))  # the block takes generic / mixed activations (and dropouts) layer by layer
-        if any(l.linear.weight.dtype != emb.node.weight.dtype for l in layers):
+        # under bf16 autocast the pair is one lower-precision op: fp32 and bf16 tensors may meet
+        bf16_compute = autocast_bf16_applies(
+            emb.node.weight.device, emb.node.weight.shape[1],
+            [emb.node.weight, emb.edge.weight] + [p for l in layers for p in (l.linear.weight, l.linear.bias)])
+        if not bf16_compute and any(l.linear.weight.dtype != emb.node.weight.dtype for l in layers):
             raise RuntimeError("embedding tables and layer weights must share one dtype")
         act = codes[0] if codes else (NT_ACT_IDENTITY, 0.0)
         residual = bool(layers) and isinstance(blk.layers[0], Residual)
@@ -156,14 +169,15 @@ class EmbeddedChempropBlock(nn.Module):
             node, H = _engine.EmbeddedBlockFunction.apply(
                 emb.node.weight, emb.edge.weight, node_types, edge_types, G.edge_index, G.rev_index.contiguous(),
                 lay, layers[0].act if layers else nn.Identity(), act, blk.reduce, residual, len(layers),
-                _dropout(layers), validate, *[l.linear.weight for l in layers], *[l.linear.bias for l in layers],
+                _dropout(layers), validate, bf16_compute,
+                *[l.linear.weight for l in layers], *[l.linear.bias for l in layers],
             )
         else:
             node, H = _engine.block_forward_embedded(
                 emb.node.weight.detach(), node_types, emb.edge.weight.detach(), edge_types,
                 G.edge_index[0].contiguous(), G.rev_index.contiguous(), lay,
                 [l.linear.weight for l in layers], [l.linear.bias for l in layers], act, blk.reduce,
-                residual, validate=validate,
+                residual, validate=validate, bf16_compute=bf16_compute,
             )
         # type indices validated for these tensors: no host sync on the next call
         lay.embed_checked = (weakref.ref(node_types), weakref.ref(edge_types), key)

@@ -12,10 +12,16 @@ from the collated integer type indices: both embedding tables are in the optimiz
 Xv / Xe leaves.  --embed-bwd kernel (default) is the kernel path (EmbeddedBlockFunction: fused init,
 nt_embed_bag_backward for the tables); --embed-bwd torch is the library path that preceded it
 (block(embedding(G)) with nn.EmbeddingBag under autograd, NT_EMBED_BWD=torch).
+--autocast (with --dtype f32) is mixed precision as Lightning's precision="bf16-mixed" runs it: the
+module, its gradients and the Adam state stay fp32, and the forward and the loss of every step run
+inside torch.autocast("cuda", dtype=torch.bfloat16), so the block computes on the bf16 kernels.
+The table and the JSON also report torch.cuda.max_memory_allocated over the timed steps.
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
-                                  [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--json]"""
+                                  [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--autocast]
+                                  [--json]"""
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -52,8 +58,16 @@ def main():
     p.add_argument("--embed-bwd", default="kernel", choices=["kernel", "torch"],
                    help="with --embedded: kernel = the fused kernel path; torch = block(embedding(G)) with "
                         "nn.EmbeddingBag under autograd (NT_EMBED_BWD=torch)")
+    p.add_argument("--autocast", action="store_true",
+                   help="fp32 module (--dtype f32) with the forward and the loss of every step inside "
+                        "torch.autocast('cuda', dtype=torch.bfloat16): fp32 master weights, bf16 kernels")
     p.add_argument("--json", action="store_true", help="print one JSON object instead of the table")
     a = p.parse_args()
+    if a.autocast and a.dtype != "f32":
+        p.error("--autocast trains an fp32 module: use --dtype f32")
+
+    def region():
+        return torch.autocast("cuda", dtype=torch.bfloat16) if a.autocast else contextlib.nullcontext()
     from notorch_amd import _lib
 
     _lib.load()  # fail loudly if the HIP extension is missing
@@ -82,20 +96,23 @@ def main():
 
     def step():
         blk.zero_grad(set_to_none=True)
-        if a.embedded:
-            out = blk(Gd)
-        else:
-            Xv_d.grad = Xe_d.grad = None
-            out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
-        ro(out).float().pow(2).sum().backward()
+        with region():
+            if a.embedded:
+                out = blk(Gd)
+            else:
+                Xv_d.grad = Xe_d.grad = None
+                out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
+            loss = ro(out).float().pow(2).sum()
+        loss.backward()
         if opt is not None:
             opt.step()
 
     def fwd():
-        with torch.no_grad():
+        with torch.no_grad(), region():
             ro(blk(Gd))
 
     res = {}
+    mem = {}
     for mode in a.modes.split(","):
         os.environ["NT_BWD"] = mode
         for name, fn in (("fwd", fwd), (f"train[{mode}]", step)):
@@ -110,6 +127,7 @@ def main():
             # host's autograd / optimizer bookkeeping overlaps the device work of the previous step):
             # rounds of `chunk` steps between two events, the median round per step
             ts = []
+            torch.cuda.reset_peak_memory_stats()
             chunk = max(1, min(10, a.steps))
             for _ in range(max(1, a.steps // chunk)):
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -120,19 +138,23 @@ def main():
                 e.synchronize()
                 ts.append(s.elapsed_time(e) / chunk)
             res[name] = statistics.median(ts)
+            mem[name] = torch.cuda.max_memory_allocated()
     if a.json:
         print(json.dumps({
             "V": G.num_nodes, "E": E, "h": a.h, "depth": a.depth, "dtype": a.dtype,
             "weight_grad": os.environ.get("NT_WGRAD", "default"), "optim": a.optim,
             **({"embedded": True, "embed_bwd": a.embed_bwd} if a.embedded else {}),
+            **({"autocast": "bf16"} if a.autocast else {}),
+            "max_memory_allocated": mem,
             "warmup": a.warmup, "steps": a.steps,
             "ms": res, "edge_messages_per_s": {k: E * a.depth / (v * 1e-3) for k, v in res.items()},
         }), flush=True)
         return
     print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}"
-          + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else ""))
+          + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else "") + (" autocast=bf16" if a.autocast else ""))
     for k, v in res.items():
-        print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s")
+        print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s  "
+              f"max allocated {mem[k] / 2**20:.1f} MiB")
 
 
 if __name__ == "__main__":
