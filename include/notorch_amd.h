@@ -537,11 +537,15 @@ NT_API int nt_dmpnn_weight_grad(const void* G, const void* H, const void* S, con
                                 float act_alpha, int dtype, void* workspace, int64_t workspace_bytes,
                                 void* dW_out, void* db_out, void* stream);
 
-/* nt_dmpnn_weight_grad on the fp32 layer kernel's numerics (h <= 320, src and rev given): G and A
+/* nt_dmpnn_weight_grad on the fp32 layer kernel's numerics (fp32, src and rev given): G and A
  * scaled by powers of two from device bounds and split into two fp16 parts, three fp16 MFMA products
  * per tile (fp32-accurate: the dropped term and the split roundings are ~2^-22 relative); half the
  * MFMA work of the bf16x6 kernel.  amax_G: one device float >= max|G|; amax_HS: two device floats
- * >= max|H|, max|S| (the forward's amax chain row of this layer).  Same workspace and outputs. */
+ * >= max|H|, max|S| (the forward's amax chain row of this layer).  Same workspace and outputs.
+ * h <= 320: every row of dW against a 128-column block of A per workgroup.  320 < h <= 8192 with
+ * h % 4 == 0: dW tiled 256 x 256, the same scales, split, products and unscaling; G, H and S must be
+ * 16-byte aligned (NT_EINVAL otherwise).  Any other h above 320: NT_EUNSUPPORTED.  E = 0 zero-fills
+ * dW and db.  Two calls are bit-identical. */
 NT_API int nt_dmpnn_weight_grad_fk(const void* G, const void* H, const void* S, const int64_t* src,
                                    const int64_t* rev, int64_t V, int64_t E, int64_t h, int act,
                                    float act_alpha, const float* amax_G, const float* amax_HS, int dtype,

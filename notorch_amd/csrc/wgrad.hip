@@ -1068,6 +1068,251 @@ __global__ void __launch_bounds__(512, 1) wgrad_bf16_wide_kernel(WxArgs a) {
   }
 }
 
+// wgrad_fk_wide_kernel (fp32 storage, 320 < h <= 8192, h % 4 == 0, gathered A): wgrad_fk_kernel's
+// numerics (the same scales, two fp16 parts per operand, G1 A0 + G0 A1 + G0 A0 in fp32, two exact
+// unscaling steps, db from the unsplit G) on wgrad_bf16_wide_kernel's structure, with dW tiled in both
+// dimensions: one 512-thread workgroup per (edge chunk, 256-column block of G, kYJ-column block of A).
+// Per 32-edge step the block's G, S[src] and H[rev] rows are loaded in 16-B pieces (4 columns: h % 4
+// == 0 keeps a piece aligned and wholly inside or outside h; one load instruction of a wave reads
+// 1 KiB of one row, or 512 B of two), scaled, split and stored as 8-B pieces to double-buffered
+// [edge][column] LDS slabs of fp16 (high and low part of G and of A, rows padded by 32 B, one barrier
+// per step), and read back as MFMA operands by the transposing LDS read.  Wave w owns i-tiles
+// kYTI (w % kYWI) .. + kYTI and j-tiles 4 (w / kYWI) .. + 4 of the block.  db of an i-block's columns
+// comes from the j-block-0 workgroups of that i-block.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+constexpr int kYI = 256;                 // G columns per block
+constexpr int kYWI = 2;                  // waves along i; 8 / kYWI along j
+constexpr int kYTI = kYI / 16 / kYWI;    // i-tiles per wave
+constexpr int kYJ = (8 / kYWI) * 64;     // A columns per block
+constexpr int kYGRS = 2 * kYI + 32;      // LDS row strides in bytes (fp16 columns and 32 B of padding,
+constexpr int kYARS = 2 * kYJ + 32;      // which puts the 4 edges of a transposing read on different banks)
+constexpr int kYGPart = kK * kYGRS;      // one fp16 part of the G slab
+constexpr int kYAPart = kK * kYARS;      // one fp16 part of the A slab
+constexpr int kYBuf = 2 * (kYGPart + kYAPart);
+constexpr int kYLds = 2 * kYBuf;
+constexpr int kYMaxH = 8192;
+constexpr int kYAP = kYJ / 4;            // 16-B pieces per A row
+constexpr int kYAR = 64 / kYAP;          // A rows per load instruction of a wave
+constexpr int kYAM = kK / (8 * kYAR);    // A load instructions per thread and step
+
+struct WyArgs {
+  const float* G;
+  const float* H;
+  const float* S;
+  const int64_t* src;
+  const int64_t* rev;
+  const float* amax_G;   // [0] >= max|G|
+  const float* amax_HS;  // [0] >= max|H|, [1] >= max|S|
+  int64_t E, h;
+  int iblocks, jblocks, ksplit, chunk_steps, xcds;
+  float alpha;
+  int act;
+  float* part;     // [ksplit][h][h]
+  float* part_db;  // [ksplit][h] or NULL
+};
+
+__device__ __forceinline__ void split2s4(const float4 x, float s, f16x4& p0, f16x4& p1) {
+  const float v[4] = {x.x * s, x.y * s, x.z * s, x.w * s};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const _Float16 h0 = (_Float16)v[j];
+    p0[j] = h0;
+    p1[j] = (_Float16)(v[j] - (float)h0);
+  }
+}
+
+template <int ACT>
+__global__ void __launch_bounds__(512, 1) wgrad_fk_wide_kernel(WyArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int nb = gridDim.x;
+  int w = blockIdx.x;
+  if (a.xcds > 1 && nb % a.xcds == 0) w = (w % a.xcds) * (nb / a.xcds) + w / a.xcds;
+  const int tiles = a.iblocks * a.jblocks;
+  const int y = w / tiles, tile = w - y * tiles;
+  const int ib = tile / a.jblocks, jb = tile - ib * a.jblocks;
+  const int64_t h = a.h, i0 = (int64_t)ib * kYI, j0 = (int64_t)jb * kYJ;
+  const int64_t e_beg = (int64_t)y * a.chunk_steps * kK;
+  const int64_t e_end0 = e_beg + (int64_t)a.chunk_steps * kK;
+  const int64_t e_end = e_end0 < a.E ? e_end0 : a.E;
+  const int nsteps = e_end > e_beg ? (int)((e_end - e_beg + kK - 1) / kK) : 0;
+  const int t = threadIdx.x, lane = t & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  const bool want_db = a.part_db != nullptr && jb == 0;
+  const int eG = wg_scale_exp(a.amax_G[0]);
+  const int eA = wg_scale_exp(a.amax_HS[1] + wg_act_bound(a.amax_HS[0], a.act, a.alpha));
+  const float sG = ldexpf(1.f, eG), sA = ldexpf(1.f, eA);
+
+  // Staging.  G: a slab row is 64 pieces; lane = piece, wave w owns rows w + 8 m (m < 4).  A: a slab
+  // row is kYAP pieces; lane % kYAP = piece, wave w owns rows kYAR w + lane / kYAP + 8 kYAR m (m < kYAM).
+  const int pa = lane & (kYAP - 1), ha = lane / kYAP;
+  const int rowa0 = kYAR * wave + ha;
+  const bool oki = i0 + 4 * lane < h, okj = j0 + 4 * pa < h;
+  const int64_t ic = oki ? i0 + 4 * lane : 0, jc = okj ? j0 + 4 * pa : 0;
+  float dbacc[4] = {0.f, 0.f, 0.f, 0.f};
+
+  // one vector load per wave and step: lane k < kYAM kYAR the src of A row kYAR wave + k % kYAR +
+  // 8 kYAR (k / kYAR), lane 8 + k its rev
+  auto load_idx = [&](int s) __attribute__((always_inline)) -> int {
+    const int k = lane & 7;
+    int64_t e = e_beg + (int64_t)s * kK + kYAR * wave + (k % kYAR) + 8 * kYAR * (k / kYAR);
+    e = e < e_end ? e : e_end - 1;
+    return lane >= 16 ? 0 : (int)(lane < 8 ? a.src[e] : a.rev[e]);
+  };
+  float4 xg[4], xs[kYAM], xh[kYAM];  // raw pieces of the step in flight
+  int64_t eb_cur = 0;
+  auto load = [&](int s, int idxv) __attribute__((always_inline)) {
+    const int64_t eb = e_beg + (int64_t)s * kK;
+    eb_cur = eb;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      int64_t e = eb + wave + 8 * m;
+      e = e < e_end ? e : e_end - 1;
+      xg[m] = *reinterpret_cast<const float4*>(a.G + e * h + ic);
+    }
+#pragma unroll
+    for (int m = 0; m < kYAM; ++m) {
+      int64_t se = __builtin_amdgcn_readlane(idxv, kYAR * m), re = __builtin_amdgcn_readlane(idxv, 8 + kYAR * m);
+      if constexpr (kYAR == 2) {
+        const int s1 = __builtin_amdgcn_readlane(idxv, 2 * m + 1), r1 = __builtin_amdgcn_readlane(idxv, 9 + 2 * m);
+        se = ha ? s1 : se;
+        re = ha ? r1 : re;
+      }
+      xs[m] = *reinterpret_cast<const float4*>(a.S + se * h + jc);
+      xh[m] = *reinterpret_cast<const float4*>(a.H + re * h + jc);
+    }
+  };
+  auto store = [&](char* buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int row = wave + 8 * m;
+      const uint32_t mg = (eb_cur + row < e_end && oki) ? ~0u : 0u;
+      float4 g = xg[m];
+      g.x = __uint_as_float(__float_as_uint(g.x) & mg);
+      g.y = __uint_as_float(__float_as_uint(g.y) & mg);
+      g.z = __uint_as_float(__float_as_uint(g.z) & mg);
+      g.w = __uint_as_float(__float_as_uint(g.w) & mg);
+      if (want_db) {
+        dbacc[0] += g.x;
+        dbacc[1] += g.y;
+        dbacc[2] += g.z;
+        dbacc[3] += g.w;
+      }
+      f16x4 p0, p1;
+      split2s4(g, sG, p0, p1);
+      *reinterpret_cast<f16x4*>(buf + row * kYGRS + lane * 8) = p0;
+      *reinterpret_cast<f16x4*>(buf + kYGPart + row * kYGRS + lane * 8) = p1;
+    }
+    char* abuf = buf + 2 * kYGPart;
+#pragma unroll
+    for (int m = 0; m < kYAM; ++m) {
+      const int row = rowa0 + 8 * kYAR * m;
+      const uint32_t ma = (eb_cur + row < e_end && okj) ? ~0u : 0u;
+      float4 v;  // out of range: exact +0
+      v.x = __uint_as_float(__float_as_uint(xs[m].x - act_t<ACT>(xh[m].x, a.act, a.alpha)) & ma);
+      v.y = __uint_as_float(__float_as_uint(xs[m].y - act_t<ACT>(xh[m].y, a.act, a.alpha)) & ma);
+      v.z = __uint_as_float(__float_as_uint(xs[m].z - act_t<ACT>(xh[m].z, a.act, a.alpha)) & ma);
+      v.w = __uint_as_float(__float_as_uint(xs[m].w - act_t<ACT>(xh[m].w, a.act, a.alpha)) & ma);
+      f16x4 p0, p1;
+      split2s4(v, sA, p0, p1);
+      *reinterpret_cast<f16x4*>(abuf + row * kYARS + pa * 8) = p0;
+      *reinterpret_cast<f16x4*>(abuf + kYAPart + row * kYARS + pa * 8) = p1;
+    }
+  };
+
+  const int fr = lane & 15, g16 = lane >> 4;
+  const int wi = wave % kYWI, wj = wave / kYWI;  // i-tiles kYTI wi .. + kYTI, j-tiles 4 wj .. 4 wj + 3
+  f32x4 acc[kYTI][4];
+#pragma unroll
+  for (int x = 0; x < kYTI; ++x)
+#pragma unroll
+    for (int z = 0; z < 4; ++z) acc[x][z] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // waves whose i-tiles or j-tiles all lie past h skip the MFMAs (a whole wave: the transposing
+  // read needs every lane)
+  const bool active = i0 + 16 * kYTI * wi < h && j0 + 16 * 4 * wj < h;
+  // the transposing read of wgrad_bf16_wide_kernel (4 edges x 16 columns per 16 lanes, two reads per
+  // operand), on fp16 parts
+  const int trg = (8 * g16 + (fr >> 2)) * kYGRS + 8 * (fr & 3);
+  const int tra = (8 * g16 + (fr >> 2)) * kYARS + 8 * (fr & 3);
+  typedef short i16x4 __attribute__((ext_vector_type(4)));
+  typedef short i16x8 __attribute__((ext_vector_type(8)));
+  typedef i16x4 __attribute__((address_space(3))) * lds4_t;
+  auto frag = [&](const char* p, int rs) __attribute__((always_inline)) -> f16x8 {
+    const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)p);
+    const i16x4 up = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(p + 4 * rs));
+    const i16x8 v = __builtin_shufflevector(lo, up, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(f16x8, v);
+  };
+  auto mfma = [&](const char* gb) __attribute__((always_inline)) {
+    if (!active) return;
+    const char* ab = gb + 2 * kYGPart;
+    f16x8 fb[4][2];
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+      fb[z][0] = frag(ab + tra + 32 * (4 * wj + z), kYARS);
+      fb[z][1] = frag(ab + kYAPart + tra + 32 * (4 * wj + z), kYARS);
+    }
+#pragma unroll
+    for (int x = 0; x < kYTI; ++x) {
+      const f16x8 fa0 = frag(gb + trg + 32 * (kYTI * wi + x), kYGRS);
+      const f16x8 fa1 = frag(gb + kYGPart + trg + 32 * (kYTI * wi + x), kYGRS);
+#pragma unroll
+      for (int z = 0; z < 4; ++z) {
+        f32x4 cc = acc[x][z];
+        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa1, fb[z][0], cc, 0, 0, 0);
+        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa0, fb[z][1], cc, 0, 0, 0);
+        cc = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa0, fb[z][0], cc, 0, 0, 0);
+        acc[x][z] = cc;
+      }
+    }
+  };
+
+  // the pieces of step s + 1 are in flight while slab s is multiplied
+  int idx_next = 0;
+  if (nsteps > 0) {
+    load(0, load_idx(0));
+    if (nsteps > 1) idx_next = load_idx(1);
+    store(lds);
+  }
+  __syncthreads();
+  for (int s = 0; s < nsteps; ++s) {
+    const bool more = s + 1 < nsteps;
+    if (more) {
+      load(s + 1, idx_next);
+      if (s + 2 < nsteps) idx_next = load_idx(s + 2);
+    }
+    mfma(lds + (s & 1) * kYBuf);
+    if (more) store(lds + ((s + 1) & 1) * kYBuf);
+    __syncthreads();  // one barrier: the next slab is written, this one is read by every wave
+  }
+
+  // unscale by 2^-eG 2^-eA (two exact steps: their product may leave the fp32 range)
+  const float iG = ldexpf(1.f, -eG), iA = ldexpf(1.f, -eA);
+  float* P = a.part + (int64_t)y * h * h;
+#pragma unroll
+  for (int x = 0; x < kYTI; ++x)
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+      const int64_t col = j0 + 16 * (4 * wj + z) + fr;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t row = i0 + 16 * (kYTI * wi + x) + 4 * g16 + q;
+        if (row < h && col < h) P[row * h + col] = (acc[x][z][q] * iG) * iA;
+      }
+    }
+  if (want_db) {  // fixed-order column sums over the 8 waves (deterministic)
+    float* red = reinterpret_cast<float*>(lds);  // the slabs are dead after the last barrier
+#pragma unroll
+    for (int c = 0; c < 4; ++c) red[wave * kYI + 4 * lane + c] = dbacc[c];
+    __syncthreads();
+    if (t < kYI && i0 + t < h) {
+      float sum = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) sum += red[k * kYI + t];
+      a.part_db[(int64_t)y * h + i0 + t] = sum;
+    }
+  }
+}
+
 // dW and db partials reduced in one launch: index i < n1 sums part[y][i] into out1[i], the rest sums
 // part_db[y][i - n1] into out2, each in ascending y (fixed order: deterministic)
 __global__ void __launch_bounds__(256) wgrad_reduce2_kernel(const float* __restrict__ part, int64_t n1,
@@ -1147,6 +1392,22 @@ WPlan make_wide_plan(int64_t E, int64_t h, int jcols = kWJ) {
 WPlan make_bf16_wide_plan(int64_t E, int64_t h) {
   WPlan p;
   const int64_t tiles = ((h + kXI - 1) / kXI) * ((h + kXJ - 1) / kXJ);
+  const int64_t steps = (E + kK - 1) / kK;
+  int64_t ks = (cu_count() > 0 ? cu_count() : 256) / tiles;
+  if (ks < 1) ks = 1;
+  if (ks > steps) ks = steps > 0 ? steps : 1;
+  p.chunk_steps = (int)((steps + ks - 1) / ks);
+  if (p.chunk_steps < 1) p.chunk_steps = 1;
+  p.ksplit = (int)((steps + p.chunk_steps - 1) / p.chunk_steps);
+  if (p.ksplit < 1) p.ksplit = 1;
+  return p;
+}
+
+// the fp32 wide kernel: one workgroup per CU, ksplit = CUs / (i-blocks x j-blocks) chunks (at least one).
+// Its blocks are at least 128 columns wide, so never more chunks than make_wide_plan(E, h, kFJ)'s.
+WPlan make_fk_wide_plan(int64_t E, int64_t h) {
+  WPlan p;
+  const int64_t tiles = ((h + kYI - 1) / kYI) * ((h + kYJ - 1) / kYJ);
   const int64_t steps = (E + kK - 1) / kK;
   int64_t ks = (cu_count() > 0 ? cu_count() : 256) / tiles;
   if (ks < 1) ks = 1;
@@ -1329,7 +1590,8 @@ extern "C" int nt_dmpnn_weight_grad_fk(const void* G, const void* H, const void*
   NT_REQUIRE(dtype == NT_F32, NT_EUNSUPPORTED, "nt_dmpnn_weight_grad_fk: fp32 only");
   NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
   NT_REQUIRE(V >= 0 && E >= 0 && h > 0, NT_EINVAL, "bad sizes");
-  NT_REQUIRE(h <= kWI, NT_EUNSUPPORTED, "nt_dmpnn_weight_grad_fk: h <= 320 (use nt_dmpnn_weight_grad)");
+  NT_REQUIRE(h <= kWI || (h % 4 == 0 && h <= kYMaxH), NT_EUNSUPPORTED,
+             "nt_dmpnn_weight_grad_fk: h <= 320, or h % 4 == 0 and h <= 8192 (else nt_dmpnn_weight_grad)");
   NT_REQUIRE(V < ((int64_t)1 << 31) && E < ((int64_t)1 << 31), NT_EUNSUPPORTED,
              "nt_dmpnn_weight_grad_fk: V and E must be < 2^31");
   NT_REQUIRE(dW_out, NT_EINVAL, "NULL dW_out");
@@ -1342,6 +1604,38 @@ extern "C" int nt_dmpnn_weight_grad_fk(const void* G, const void* H, const void*
   NT_REQUIRE(G && S && H && src && rev && amax_G && amax_HS, NT_EINVAL, "NULL pointer");
   NT_REQUIRE(workspace && workspace_bytes >= nt_dmpnn_weight_grad_workspace(E, h), NT_EINVAL,
              "workspace too small (nt_dmpnn_weight_grad_workspace)");
+  if (h > kWI) {  // dW tiled in both dimensions
+    NT_REQUIRE(((uintptr_t)G | (uintptr_t)H | (uintptr_t)S) % 16 == 0, NT_EINVAL,
+               "nt_dmpnn_weight_grad_fk: h > 320 needs 16-byte aligned G, H and S");
+    const WPlan q = make_fk_wide_plan(E, h);
+    WyArgs b;
+    b.G = (const float*)G;
+    b.H = (const float*)H;
+    b.S = (const float*)S;
+    b.src = src;
+    b.rev = rev;
+    b.amax_G = amax_G;
+    b.amax_HS = amax_HS;
+    b.E = E;
+    b.h = h;
+    b.iblocks = (int)((h + kYI - 1) / kYI);
+    b.jblocks = (int)((h + kYJ - 1) / kYJ);
+    b.ksplit = q.ksplit;
+    b.chunk_steps = q.chunk_steps;
+    b.xcds = xcd_count();
+    b.alpha = act_alpha;
+    b.act = act;
+    b.part = (float*)workspace;
+    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
+    const int grid = b.iblocks * b.jblocks * q.ksplit;
+    auto kern = act == NT_ACT_IDENTITY ? wgrad_fk_wide_kernel<NT_ACT_IDENTITY>
+                : act == NT_ACT_RELU   ? wgrad_fk_wide_kernel<NT_ACT_RELU>
+                                       : wgrad_fk_wide_kernel<-1>;
+    NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kYLds));
+    kern<<<grid, 512, kYLds, stream>>>(b);
+    NT_LAUNCH_CHECK();
+    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
+  }
   const WPlan q = make_wide_plan(E, h, kFJ);
   WfArgs b;
   b.G = (const float*)G;

@@ -1000,10 +1000,12 @@ def weight_grad(G: Tensor, H: Tensor | None, S: Tensor, src: Tensor | None, rev:
                 amax_G: Tensor | None = None, amax_HS: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
     """(dW, db) = (G^T A, sum_e G[e]) with A[e] = S[src e] - act(H[rev e]) formed on the fly
     (src = rev = None: A = S).  Split-K, deterministic.  fp32: with amax_G (1 device float >= max|G|)
-    and amax_HS (2 floats >= max|H|, max|S|), h <= 320 and src / rev given, the two-part fp16 kernel
-    (nt_dmpnn_weight_grad_fk); else the bf16x6 kernel.  bf16 (src / rev given; an even h <= 512, or
-    h % 8 == 0 up to 8192 on the kernel that tiles dW in both dimensions): A rounded to bf16 as the
-    forward's message, one bf16 MFMA per tile; dW and db come back in fp32."""
+    and amax_HS (2 floats >= max|H|, max|S|), src / rev given, and h <= 320 or h % 4 == 0 up to 8192
+    with 16-byte aligned G, H and S (above 320 on the kernel that tiles dW in both dimensions), the
+    two-part fp16 kernel (nt_dmpnn_weight_grad_fk); every other call the bf16x6 kernel.  bf16 (src /
+    rev given; an even h <= 512, or h % 8 == 0 up to 8192 on the kernel that tiles dW in both
+    dimensions): A rounded to bf16 as the forward's message, one bf16 MFMA per tile; dW and db come
+    back in fp32."""
     dev = _require_device(G, H, S, src, rev, amax_G, amax_HS)
     code = _require_feat("G", G)
     _require_feat("S", S, G.dtype)
@@ -1044,7 +1046,10 @@ def weight_grad(G: Tensor, H: Tensor | None, S: Tensor, src: Tensor | None, rev:
     ws = torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
     dW = torch.empty(h, h, dtype=torch.float32, device=dev)
     db = torch.empty(h, dtype=torch.float32, device=dev) if bias else None
-    if code == NT_F32 and amax_G is not None and amax_HS is not None and src is not None and h <= 320:
+    fk = code == NT_F32 and amax_G is not None and amax_HS is not None and src is not None
+    if fk and h > 320:  # the kernel that tiles dW in both dimensions: 16-B row pieces
+        fk = h % 4 == 0 and h <= 8192 and all(t.data_ptr() % 16 == 0 for t in (G, H, S))
+    if fk:
         _require_amax(amax_G, G.dtype, n=1)
         _require_amax(amax_HS, G.dtype)
         _run(dev, lib.nt_dmpnn_weight_grad_fk, _ptr(G), _ptr(H), _ptr(S), _ptr(src), _ptr(rev), S.shape[0], E,

@@ -1,7 +1,9 @@
 """Micro-benchmark of the individual fp32 forward kernels on one qm9-shaped batch (device time via
 torch.cuda events, interleaved rounds in one process).  Also the driver for the per-kernel PMC passes
 (tools/pmc_update.sh).  Usage: python tools/kbench.py [--mols 4096] [--h 300] [--only fk_fused,init]
---only wgrad_bf16 [--kind zinc --h 1024]: the bf16 weight-gradient kernel beside the library route."""
+--only wgrad_bf16 [--kind zinc --h 1024]: the bf16 weight-gradient kernel beside the library route.
+--only wgrad_fk [--kind zinc --h 1024]: the fp32 fp16-split weight-gradient kernel beside the bf16x6
+kernel and the library route."""
 import argparse
 import os
 import statistics
@@ -77,6 +79,60 @@ def wgrad_bf16(G, h, rounds):
         print(f"{name:18s} median {med:8.1f} us  min {mn:8.1f} us{extra}")
 
 
+def wgrad_fk(G, h, rounds):
+    """fp32 weight gradient of one layer on the batch's graph, three routes in interleaved rounds:
+    K.weight_grad with bounds (nt_dmpnn_weight_grad_fk: the fp16-split kernel), K.weight_grad without
+    bounds (nt_dmpnn_weight_grad: the bf16x6 kernel) and the library route (dmpnn_message + split-K
+    library GEMM + column sum).  Prints each median and the fk kernel's algorithmic bytes and roofs."""
+    from notorch_amd.nn.gnn import _engine
+
+    V, E = G.num_nodes, G.num_edges
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    Gr = torch.randn(E, h, device="cuda", generator=gen)
+    H = torch.randn(E, h, device="cuda", generator=gen)
+    S = torch.randn(V, h, device="cuda", generator=gen)
+    src, rev = G.edge_index[0].contiguous(), G.rev_index
+    relu = K.act_code(torch.nn.ReLU())
+    amax_G, amax_HS = torch.zeros(1, device="cuda"), torch.zeros(2, device="cuda")
+    K.absmax(Gr, amax_G)
+    K.absmax(H, amax_HS[0:1])
+    K.absmax(S, amax_HS[1:2])
+
+    def library():
+        A = K.dmpnn_message(H, S, src, rev, act=relu)
+        return _engine._weight_grad(Gr, A), Gr.sum(0)
+
+    fns = {"wgrad_fk": lambda: K.weight_grad(Gr, H, S, src, rev, act=relu, amax_G=amax_G, amax_HS=amax_HS),
+           "wgrad_x6": lambda: K.weight_grad(Gr, H, S, src, rev, act=relu),
+           "wgrad_library": library}
+    dW, db = fns["wgrad_fk"]()
+    dW6, _ = fns["wgrad_x6"]()
+    dWl, dbl = library()
+    torch.cuda.synchronize()
+    scale = dW.abs().max().item()
+    print(f"V={V} E={E} h={h} fp32: max |dW fk - dW x6| / max|dW| = {(dW - dW6).abs().max().item() / scale:.2e}, "
+          f"max |dW fk - dW library| / max|dW| = {(dW - dWl).abs().max().item() / scale:.2e}")
+    res = {n: [] for n in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            res[name].append(timeit(f, 10))
+    # the fk kernel's traffic: above h = 320 dW is tiled 256 x 256 (G is read once per j-block and the
+    # two gathers once per i-block), up to 320 all of G per 128-column block of A and the gathers once
+    ib, jb = ((h + 255) // 256, (h + 255) // 256) if h > 320 else (1, (h + 127) // 128)
+    once = 3 * E * h * 4
+    loaded = (jb + 2 * ib) * E * h * 4
+    t_hbm, t_mfma = once / HBM_PEAK, 3 * 2 * E * h * h / BF16_MFMA_PEAK  # three fp16 products
+    for name in fns:
+        med = statistics.median(r[0] for r in res[name])
+        mn = min(r[1] for r in res[name])
+        extra = ""
+        if name == "wgrad_fk":
+            extra = (f"  loads {loaded / 1e9:.2f} GB ({loaded / (med * 1e-6) / 1e12:.2f} TB/s), operands once "
+                     f"{once / 1e9:.2f} GB: HBM roof {t_hbm * 1e6:.1f} us ({t_hbm / (med * 1e-6):.1%}), "
+                     f"MFMA roof {t_mfma * 1e6:.1f} us ({t_mfma / (med * 1e-6):.1%})")
+        print(f"{name:18s} median {med:8.1f} us  min {mn:8.1f} us{extra}")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--mols", type=int, default=4096)
@@ -89,6 +145,8 @@ def main():
     G = make_batch(a.kind, a.mols, seed=0).collate("nodes").to("cuda")
     if a.only == "wgrad_bf16":  # bf16 operands of its own; none of the fp32 set-up below
         return wgrad_bf16(G, a.h, a.rounds)
+    if a.only == "wgrad_fk":
+        return wgrad_fk(G, a.h, a.rounds)
     V, E, h = G.num_nodes, G.num_edges, a.h
     lay = G._nt_layout
     gen = torch.Generator(device="cuda").manual_seed(0)
