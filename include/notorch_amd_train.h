@@ -89,6 +89,38 @@ NT_API int nt_dmpnn_init_embed_mixed(const void* node_table, int64_t num_node_ty
                                      int64_t V, int64_t E, int64_t h, int act, float act_alpha,
                                      int reduce, void* H0, void* S, void* stream);
 
+/*
+ * nt_dmpnn_update_fused for a layer whose update passes training-mode dropout (notorch/nn/gnn/
+ * chemprop.py:26 `update = Sequential(Linear, Dropout(p))` under residual.py:28), in the same ONE
+ * persistent launch per layer:
+ *   U[e]        = W (S[src[e]] - act(H[rev[e]])) + b
+ *   H_out[e, j] = (residual ? H[e, j] : 0) + keep(seed, offset + e * h + j) * U[e, j] / (1 - p)
+ *   S_out[v]    = reduce_{dst[e] = v} agg_act(H_out[e])                       (as nt_dmpnn_update_fused)
+ * keep() is bit for bit the decision of nt_dropout_residual(p, seed, offset) on the dense E x h
+ * element index e * h + j (whatever the row pitch), so the backward regenerates the mask with that
+ * entry point; p = 1 drops everything (H_out = the residual term).  The mask is applied in the layer
+ * kernel's epilogue: fp32 in update_fk_kernel (every walk of the fused plan: 128-row tiles, 64-row
+ * tiles of one or two workgroups per CU, column chunks above h = 512, hub sub-run partials S_part),
+ * where amax_out receives max|H_out| and max|S_out| of the values after dropout; bf16 in the 64-row
+ * layer kernel and its h > 512 variant, keep * (acc + b) / (1 - p) + H in fp32 with one rounding (the
+ * unfused sequence rounds U and H_out), the aggregation reading the rounded value.
+ *
+ * Arguments, shape, alignment and dtype rules: those of nt_dmpnn_update_fused, plus
+ * 0 <= p <= 1 (else NT_EINVAL, checked on the host before anything else).  A tile plan is required
+ * (tile_ptr != NULL, with S_out; NT_EUNSUPPORTED without one: callers without a plan run
+ * nt_dmpnn_update + nt_dropout_residual); bf16 takes plans of at most 64 rows with perm and
+ * dst_sorted.  nt_last_kernel() names the variant ("..., dropout in the epilogue").
+ */
+NT_API int nt_dmpnn_update_fused_dropout(const void* H, const void* S, const int64_t* src, const int64_t* rev,
+                                         const void* Wp, const void* b, int64_t V, int64_t E, int64_t h,
+                                         int residual, int act, float act_alpha, const int32_t* tile_ptr,
+                                         int64_t ntiles, int tile_rows, int max_in_degree, const int32_t* perm,
+                                         const int32_t* dst_sorted, const void* row_table, int reduce,
+                                         int agg_act, float agg_alpha, int dtype, const float* amax_in,
+                                         float* amax_out, void* H_out, void* S_out, void* S_part,
+                                         int64_t ld_in, int64_t ld_out, float p, uint64_t seed, uint64_t offset,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,13 @@ EXT_SIGNATURES: dict[str, tuple] = {
         [_vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64,
          _c_int, _c_f32, _c_int, _vp, _vp, _vp],
     ),
+    # nt_dmpnn_update_fused + (p, seed, offset) ahead of the stream: dropout in the layer kernel's epilogue
+    "nt_dmpnn_update_fused_dropout": (
+        _c_int,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_f32, _vp, _c_i64,
+         _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_f32, _c_int, _vp, _vp, _vp, _vp, _vp, _c_i64,
+         _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp],
+    ),
 }
 
 

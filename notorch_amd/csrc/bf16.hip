@@ -226,12 +226,16 @@ __device__ __forceinline__ void reduce_rows(const float* stage, int r0, int r1, 
 
 // AGG: 0 = no aggregation; 1 = fused aggregation of the stored H' (final node scatter, identity);
 // 2 = fused aggregation of act(H') (the next layer's chemprop.py:37-39, same act as this layer)
-template <int ACT, int W, int NW, int AGG>
+// DROP (nt_dmpnn_update_fused_dropout): the update passes the dropout mask `drop` (dropout.hpp, dense
+// element index e h + j) before the residual is added, H' = H + keep (stage + bias) / (1 - p), in fp32
+// with one rounding; the aggregation reads the rounded value as without dropout.
+template <int ACT, int W, int NW, int AGG, bool DROP = false>
 __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
     const bf16_t* __restrict__ H, const bf16_t* __restrict__ S, const int64_t* __restrict__ src,
     const int64_t* __restrict__ rev, const uint4* __restrict__ Wp, const bf16_t* __restrict__ bias,
     int64_t V, int64_t E, int h, int KS, int NTn, int residual, int act, float alpha,
-    bf16_t* __restrict__ out, BfAgg agg, int ntiles, int nxcd) {
+    bf16_t* __restrict__ out, BfAgg agg, int ntiles, int nxcd, DropMask drop) {
+  static_assert(!DROP || (W == 8 && AGG != 0), "dropout: the fused kernel on whole 16-B pieces only");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ int64_t soff[kM], qoff[kM], erow[kM];
   __shared__ int nstart[kM + 1], nnode[kM], nseg;
@@ -480,7 +484,9 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
 #pragma unroll
           for (int q = 0; q < 8; ++q) {
             const unsigned hb = (q & 1) ? (hu[q >> 1] & 0xffff0000u) : (hu[q >> 1] << 16);
-            y[q] = st[q] + bb[q] + (residual ? __uint_as_float(hb) : 0.f);
+            float u = st[q] + bb[q];
+            if constexpr (DROP) u = drop_apply(drop, (uint64_t)(e * h + n0 + cpiece + q), u);
+            y[q] = u + (residual ? __uint_as_float(hb) : 0.f);
           }
           if constexpr ((BF_ABL & 4) == 0) store_chunk<8>(out + e * h + n0 + cpiece, y);
           if constexpr (AGG != 0) {  // the aggregation reads the stored (bf16) value, as unfused
@@ -538,12 +544,13 @@ constexpr int kLdaW = a_row_bytes(kKSc);      // 1040 B
 constexpr int kLdsW = kM * kLdaW > kStageB ? kM * kLdaW : kStageB;  // 66,560 B
 constexpr int kNTp = 4 * kNWMax;              // column tiles per pass (32 = 512 columns)
 
-template <int ACT, int AGG>
+template <int ACT, int AGG, bool DROP = false>
 __global__ void __launch_bounds__(kThreads, 2) update_bf16_wide_kernel(
     const bf16_t* __restrict__ H, const bf16_t* __restrict__ S, const int64_t* __restrict__ src,
     const int64_t* __restrict__ rev, const uint4* __restrict__ Wp, const bf16_t* __restrict__ bias,
     int64_t V, int64_t E, int h, int KS, int NTn, int residual, int act, float alpha,
-    bf16_t* __restrict__ out, BfAgg agg, int ntiles, int nxcd) {
+    bf16_t* __restrict__ out, BfAgg agg, int ntiles, int nxcd, DropMask drop) {
+  static_assert(!DROP || AGG != 0, "dropout: the fused kernel only");
   constexpr int NW = kNWMax;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ int64_t soff[kM], qoff[kM], erow[kM];
@@ -756,7 +763,9 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_wide_kernel(
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
               const unsigned hb = (q & 1) ? (hu[q >> 1] & 0xffff0000u) : (hu[q >> 1] << 16);
-              y[q] = st[q] + bb[q] + (residual ? __uint_as_float(hb) : 0.f);
+              float u = st[q] + bb[q];
+              if constexpr (DROP) u = drop_apply(drop, (uint64_t)(e * h + n0 + cpiece + q), u);
+              y[q] = u + (residual ? __uint_as_float(hb) : 0.f);
             }
             store_chunk<8>(out + e * h + n0 + cpiece, y);
             if constexpr (AGG != 0) {  // the aggregation reads the stored (bf16) value, as unfused
@@ -803,21 +812,22 @@ static bool valid_reduce(int r) { return r >= NT_SUM && r <= NT_MIN; }
     }                                                                                           \
   } while (0)
 
-template <int ACT, int W, int NW, int AGG>
+template <int ACT, int W, int NW, int AGG, bool DROP = false>
 int launch_upd(const void* H, const void* S, const int64_t* src, const int64_t* rev, const void* Wp,
                const void* b, int64_t V, int64_t E, int64_t h, int residual, int act, float alpha,
-               void* H_out, int64_t grid, const BfAgg& agg, hipStream_t stream) {
+               void* H_out, int64_t grid, const BfAgg& agg, hipStream_t stream, const DropMask& drop = DropMask{}) {
   const int KS = (int)((h + 31) / 32), NTn = (int)((h + 15) / 16);
   const int lds = lds_bytes_bf16(KS);
-  auto kern = update_bf16_kernel<ACT, W, NW, AGG>;
+  auto kern = update_bf16_kernel<ACT, W, NW, AGG, DROP>;
   if (lds > 64 * 1024)
     NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   const int64_t slots = 2 * (int64_t)cu_count();  // two resident workgroups per CU (LDS-bound)
   const int64_t g = grid < slots ? grid : slots;
-  set_last_kernel("update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles");
+  set_last_kernel(DROP ? "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles, dropout in the epilogue"
+                       : "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles");
   kern<<<(unsigned)g, kThreads, lds, stream>>>(
       (const bf16_t*)H, (const bf16_t*)S, src, rev, (const uint4*)Wp, (const bf16_t*)b, V, E, (int)h,
-      KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count());
+      KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count(), drop);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -897,17 +907,17 @@ int pack_weight_bf16(const void* W, int64_t nlayers, int64_t h, int64_t layer_st
   return NT_OK;
 }
 
-template <int ACT, int W, int AGG>
+template <int ACT, int W, int AGG, bool DROP = false>
 static int launch_upd_nw(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                          const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
                          int act, float alpha, void* H_out, int64_t grid, const BfAgg& agg,
-                         hipStream_t stream) {
+                         hipStream_t stream, const DropMask& drop = DropMask{}) {
   const int nw = (int)(((h + 15) / 16 + 3) / 4);
   switch (nw) {
 #define NT_NW(N)                                                                                  \
   case N:                                                                                         \
-    return launch_upd<ACT, W, N, AGG>(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha, H_out, \
-                                      grid, agg, stream);
+    return launch_upd<ACT, W, N, AGG, DROP>(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha, H_out, \
+                                            grid, agg, stream, drop);
     NT_NW(1) NT_NW(2) NT_NW(3) NT_NW(4) NT_NW(5) NT_NW(6) NT_NW(7) NT_NW(8)
 #undef NT_NW
   }
@@ -916,20 +926,22 @@ static int launch_upd_nw(const void* H, const void* S, const int64_t* src, const
 }
 
 // h > 512: the column-pass / K-chunk kernel (whole 16-B pieces only)
-template <int ACT, int AGG>
+template <int ACT, int AGG, bool DROP = false>
 static int launch_upd_wide(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                            const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
                            int act, float alpha, void* H_out, int64_t grid, const BfAgg& agg,
-                           hipStream_t stream) {
+                           hipStream_t stream, const DropMask& drop = DropMask{}) {
   const int KS = (int)((h + 31) / 32), NTn = (int)((h + 15) / 16);
-  auto kern = update_bf16_wide_kernel<ACT, AGG>;
+  auto kern = update_bf16_wide_kernel<ACT, AGG, DROP>;
   NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsW));
   const int64_t slots = 2 * (int64_t)cu_count();
   const int64_t g = grid < slots ? grid : slots;
-  set_last_kernel("update_bf16_kernel: wide (h > 512), column passes x K chunks of 512, 64-edge tiles");
+  set_last_kernel(DROP ? "update_bf16_kernel: wide (h > 512), column passes x K chunks of 512, 64-edge tiles, "
+                         "dropout in the epilogue"
+                       : "update_bf16_kernel: wide (h > 512), column passes x K chunks of 512, 64-edge tiles");
   kern<<<(unsigned)g, kThreads, kLdsW, stream>>>(
       (const bf16_t*)H, (const bf16_t*)S, src, rev, (const uint4*)Wp, (const bf16_t*)b, V, E, (int)h,
-      KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count());
+      KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count(), drop);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -967,7 +979,9 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
                              const void* Wp, const void* b, int64_t V, int64_t E, int64_t h,
                              int residual, int act, float alpha, const int32_t* tile_ptr,
                              int64_t ntiles, const int32_t* perm, const int32_t* dsts, int reduce,
-                             int aact, float aalpha, void* H_out, void* S_out, hipStream_t stream) {
+                             int aact, float aalpha, void* H_out, void* S_out, hipStream_t stream,
+                             const DropMask* drop) {
+  NT_REQUIRE(drop == nullptr || tile_ptr != nullptr, NT_EUNSUPPORTED, "the dropout layer kernel needs a tile plan");
   if (tile_ptr == nullptr)  // no plan: the plain (unfused) kernel computes H_out only
     return launch_update_bf16(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha, H_out, stream);
   NT_REQUIRE(bf16_fused_supported(h), NT_EUNSUPPORTED, "bf16 update_fused needs h % 8 == 0, h <= 8192");
@@ -979,6 +993,22 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
   NT_REQUIRE(aact == NT_ACT_IDENTITY || (aact == act && aalpha == alpha), NT_EUNSUPPORTED,
              "bf16 update_fused: agg_act must be identity or equal to act");
   const BfAgg agg{tile_ptr, perm, dsts, reduce, aact, aalpha, (bf16_t*)S_out};
+  if (drop) {
+    // the same kernels, the update masked before the residual is added; relu or the run-time
+    // activation switch (identity included) to keep the instance count down
+#define NT_BF_DROP(KERN, ...)                                                                              \
+  return act == NT_ACT_RELU ? KERN<NT_ACT_RELU, __VA_ARGS__>(H, S, src, rev, Wp, b, V, E, h, residual, act, \
+                                                             alpha, H_out, ntiles, agg, stream, *drop)     \
+                            : KERN<-1, __VA_ARGS__>(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha,  \
+                                                    H_out, ntiles, agg, stream, *drop)
+    if (h > 4 * kNWMax * 16) {
+      if (aact == NT_ACT_IDENTITY) NT_BF_DROP(launch_upd_wide, 1, true);
+      NT_BF_DROP(launch_upd_wide, 2, true);
+    }
+    if (aact == NT_ACT_IDENTITY) NT_BF_DROP(launch_upd_nw, 8, 1, true);
+    NT_BF_DROP(launch_upd_nw, 8, 2, true);
+#undef NT_BF_DROP
+  }
   if (h > 4 * kNWMax * 16) {
     NT_REQUIRE(aligned16(H) && aligned16(S) && aligned16(H_out) && (b == nullptr || aligned16(b)), NT_EINVAL,
                "bf16 with h > 512 needs 16-byte aligned feature pointers");

@@ -4,6 +4,7 @@
 #include <utility>
 
 #include "common.hpp"
+#include "dropout.hpp"
 
 namespace nt {
 
@@ -54,9 +55,11 @@ int launch_update_pk(const UpdateArgs& u, const int32_t* tile_ptr, int64_t ntile
 // fp16x3 persistent layer kernel (update_fk.hpp, built in update_pk.hip): any h % 4 == 0; tiles of
 // at most fk_tile_rows(h, act, reduce, aact, fused) rows; Wimg = the fk image of the layer (header + fragment blocks).
 int fk_tile_rows(int64_t h, int act, int reduce, int aact, bool fused);
+// drop (fused plans only): the update passes this dropout mask before the residual is added
 int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in, float* amax_out,
                      const int32_t* tile_ptr, int64_t ntiles, int tile_rows, int max_in_degree,
-                     const void* row_table, int reduce, int aact, float aalpha, float* S_out);
+                     const void* row_table, int reduce, int aact, float aalpha, float* S_out,
+                     const DropMask* drop = nullptr);
 // fk images of nlayers separate weights (<= 16) and optionally of their transposes, one launch pair
 int fk_pack_multi(const float* const* W, int64_t nlayers, int64_t h, char* const* img, char* const* imgT,
                   hipStream_t stream);

@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include "update.hpp"
+#include "../../include/notorch_amd_train.h"
 
 namespace nt {
 
@@ -742,17 +743,16 @@ extern "C" int nt_dmpnn_update(const void* H, const void* S, const int64_t* src,
                           (float*)H_out, vec, stream);
 }
 
-extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t* src,
-                                     const int64_t* rev, const void* Wp, const void* b, int64_t V,
-                                     int64_t E, int64_t h, int residual, int act, float act_alpha,
-                                     const int32_t* tile_ptr, int64_t ntiles, int tile_rows,
-                                     int max_in_degree, const int32_t* perm,
-                                     const int32_t* dst_sorted, const void* row_table, int reduce,
-                                     int agg_act, float agg_alpha, int dtype, const float* amax_in,
-                                     float* amax_out, void* H_out, void* S_out, void* S_part, int64_t ld_in,
-                                     int64_t ld_out, void* stream_) {
+// nt_dmpnn_update_fused (drop == NULL) and nt_dmpnn_update_fused_dropout (the update masked by *drop
+// before the residual is added; fused plans only): one set of shape, alignment and dtype rules
+static int update_fused(const void* H, const void* S, const int64_t* src, const int64_t* rev, const void* Wp,
+                        const void* b, int64_t V, int64_t E, int64_t h, int residual, int act, float act_alpha,
+                        const int32_t* tile_ptr, int64_t ntiles, int tile_rows, int max_in_degree,
+                        const int32_t* perm, const int32_t* dst_sorted, const void* row_table, int reduce,
+                        int agg_act, float agg_alpha, int dtype, const float* amax_in, float* amax_out,
+                        void* H_out, void* S_out, void* S_part, int64_t ld_in, int64_t ld_out, void* stream_,
+                        const nt::DropMask* drop) {
   using namespace nt;
-  clear_error();
   NT_REQUIRE(ld_in >= 0 && ld_out >= 0, NT_EINVAL, "bad row pitch");
   NT_REQUIRE(dtype == NT_F32 || ((ld_in == 0 || ld_in == h) && (ld_out == 0 || ld_out == h) && S_part == nullptr),
              NT_EUNSUPPORTED, "row pitches other than h and hub partials are fp32 only");
@@ -766,6 +766,10 @@ extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t
              "update_fused needs h % 4 == 0 (fp32) or h % 8 == 0 (bf16), h <= 8192");
   if (E == 0) return NT_OK;
   NT_REQUIRE(H && S && src && rev && Wp && H_out, NT_EINVAL, "NULL pointer");
+  if (drop) {
+    NT_REQUIRE(tile_ptr != nullptr || S_out == nullptr, NT_EINVAL, "S_out must be given exactly with a tile plan");
+    NT_REQUIRE(tile_ptr != nullptr, NT_EUNSUPPORTED, "the dropout layer kernel needs a tile plan");
+  }
   NT_REQUIRE(H != H_out && (S_out == nullptr || S_out != S), NT_EINVAL, "outputs alias inputs");
   NT_REQUIRE(aligned16(H) && aligned16(S) && aligned16(H_out) && aligned16(Wp) &&
                  (b == nullptr || aligned16(b)) && (S_out == nullptr || aligned16(S_out)),
@@ -774,7 +778,8 @@ extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t
     // the fk skeleton (128-row tiles) when the plan comes with its row table, else the 64-row kernel;
     // the one-wave-per-SIMD walk for fused relu / sum layers whose plan has a row table
     const bool fwb = tile_ptr != nullptr && row_table != nullptr && fw_active(h, NT_BF16, act, reduce, agg_act);
-    if ((bf16_fk(h) || fwb) && (tile_ptr == nullptr || row_table != nullptr)) {
+    // (dropout runs in the 64-row kernel's epilogue only, whatever NT_BF16_KERNEL selects)
+    if (!drop && (bf16_fk(h) || fwb) && (tile_ptr == nullptr || row_table != nullptr)) {
       NT_REQUIRE(row_table == nullptr || aligned16(row_table), NT_EINVAL, "row_table must be 16-byte aligned");
       UpdateArgs a{(const float*)H, (const float*)S, src, rev, Wp, (const float*)b, V, E, h,
                    0, 0, residual, act, act_alpha, (float*)H_out, as_stream(stream_)};
@@ -784,7 +789,7 @@ extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t
     NT_REQUIRE(tile_ptr == nullptr || tile_rows <= 64, NT_EUNSUPPORTED, "bf16 tiles hold at most 64 rows");
     return launch_update_bf16_fused(H, S, src, rev, Wp, b, V, E, h, residual, act, act_alpha,
                                     tile_ptr, ntiles, perm, dst_sorted, reduce, agg_act, agg_alpha,
-                                    H_out, S_out, as_stream(stream_));
+                                    H_out, S_out, as_stream(stream_), drop);
   }
   UpdateArgs a{(const float*)H, (const float*)S, src, rev, Wp, (const float*)b, V, E, h,
                0, 0, residual, act, act_alpha, (float*)H_out, as_stream(stream_), ld_in, ld_out, (float*)S_part};
@@ -792,7 +797,41 @@ extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t
   NT_REQUIRE(S_part == nullptr || (tile_ptr != nullptr && aligned16(S_part)), NT_EINVAL,
              "S_part needs a tile plan and 16-byte alignment");
   return launch_update_fk(a, (const char*)Wp + fk_offset(h), amax_in, amax_out, tile_ptr, ntiles,
-                          tile_rows, max_in_degree, row_table, reduce, agg_act, agg_alpha, (float*)S_out);
+                          tile_rows, max_in_degree, row_table, reduce, agg_act, agg_alpha, (float*)S_out, drop);
+}
+
+extern "C" int nt_dmpnn_update_fused(const void* H, const void* S, const int64_t* src,
+                                     const int64_t* rev, const void* Wp, const void* b, int64_t V,
+                                     int64_t E, int64_t h, int residual, int act, float act_alpha,
+                                     const int32_t* tile_ptr, int64_t ntiles, int tile_rows,
+                                     int max_in_degree, const int32_t* perm,
+                                     const int32_t* dst_sorted, const void* row_table, int reduce,
+                                     int agg_act, float agg_alpha, int dtype, const float* amax_in,
+                                     float* amax_out, void* H_out, void* S_out, void* S_part, int64_t ld_in,
+                                     int64_t ld_out, void* stream_) {
+  nt::clear_error();
+  return update_fused(H, S, src, rev, Wp, b, V, E, h, residual, act, act_alpha, tile_ptr, ntiles, tile_rows,
+                      max_in_degree, perm, dst_sorted, row_table, reduce, agg_act, agg_alpha, dtype, amax_in,
+                      amax_out, H_out, S_out, S_part, ld_in, ld_out, stream_, nullptr);
+}
+
+extern "C" int nt_dmpnn_update_fused_dropout(const void* H, const void* S, const int64_t* src,
+                                             const int64_t* rev, const void* Wp, const void* b, int64_t V,
+                                             int64_t E, int64_t h, int residual, int act, float act_alpha,
+                                             const int32_t* tile_ptr, int64_t ntiles, int tile_rows,
+                                             int max_in_degree, const int32_t* perm,
+                                             const int32_t* dst_sorted, const void* row_table, int reduce,
+                                             int agg_act, float agg_alpha, int dtype, const float* amax_in,
+                                             float* amax_out, void* H_out, void* S_out, void* S_part,
+                                             int64_t ld_in, int64_t ld_out, float p, uint64_t seed,
+                                             uint64_t offset, void* stream_) {
+  using namespace nt;
+  clear_error();
+  NT_REQUIRE(p >= 0.f && p <= 1.f, NT_EINVAL, "dropout probability must be in [0, 1]");
+  const DropMask drop = drop_mask(p, seed, offset);
+  return update_fused(H, S, src, rev, Wp, b, V, E, h, residual, act, act_alpha, tile_ptr, ntiles, tile_rows,
+                      max_in_degree, perm, dst_sorted, row_table, reduce, agg_act, agg_alpha, dtype, amax_in,
+                      amax_out, H_out, S_out, S_part, ld_in, ld_out, stream_, &drop);
 }
 
 // out = X W^T (the layer GEMM alone: no gathers, no residual, no bias); the backward's dA = G W passes

@@ -35,11 +35,16 @@
 // (DPP row shifts within 16 lanes, carries between row tiles): the node sums come out in ascending
 // edge order, bit-identical to CPU scatter_add_ of the same H_out.  Hidden sizes beyond one chunk
 // of 128 columns x CT (h > 384 / 512) loop over column chunks, re-gathering A per chunk.
+//
+// Training-mode dropout (DROP instances, nt_dmpnn_update_fused_dropout): the epilogue passes the
+// update through the mask of dropout.hpp before the residual is added, H_out = (residual ? H : 0) +
+// keep (W A + b) / (1 - p); see update_fk_kernel.
 #pragma once
 
 #include <type_traits>
 
 #include "common.hpp"
+#include "dropout.hpp"
 
 namespace nt {
 namespace fk {
@@ -108,6 +113,7 @@ struct Args {
 #ifdef NT_DIAG
   int rtabl = 0;  // diagnostic library: the fw walk's timing ablations (NT_FK_RTABL, results invalid)
 #endif
+  DropMask drop;  // DROP instances (nt_dmpnn_update_fused_dropout): the mask of the update, indexed e h + j
 };
 
 // power-of-two scale that maps a magnitude bound to < 2^14 (exponent at most 24; every finite
@@ -473,15 +479,23 @@ struct EpiCtx {
   f32x4* SO4;
   const int4* em;
   int n;
+  const f32x4* H4 = nullptr;  // DROP instances: the residual rows, added behind the mask (NULL: none)
 };
 
-template <int RTI, int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, int PREC, int NW>
+template <int RTI, int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC,
+          int NW>
 __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, const Args& a, const EpiCtx& x0, int pc,
                                            bool pok, const f32x4& bj, f32x4& carry, float& ccnt) {
   if (16 * RTI < x0.n) {
     const int lo = st.lo;
     const int4 ri = x0.em[16 * RTI + st.fr];
     f32x4 o;
+    [[maybe_unused]] f32x4 hres = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (DROP) {
+      // the residual piece, issued ahead of the mask's hashes (no per-lane branch: rows past the tile
+      // and pieces past h read row 0 / piece 0, in bounds, and are never stored)
+      if (x0.H4) hres = x0.H4[(int64_t)(ri.x >= 0 ? ri.x : 0) * st.li + (pok ? pc : 0)];
+    }
     uint2 ob = uint2{0u, 0u};  // bf16: the stored (rounded) H_out piece
     if constexpr (PREC == 1) {
       // bf16: acc + bias in fp32, one rounding; the aggregation below reads the stored value
@@ -492,6 +506,13 @@ __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, cons
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) o[q] = fmaf(st.acc[RTI][J][q], st.inv, bj[q]);
+      if constexpr (DROP) {
+        // o is the update U alone (the accumulators started at zero): H_out = H + keep U / (1 - p),
+        // the mask indexed by the dense element e h + j as nt_dropout_residual indexes it
+        const uint64_t i0 = (uint64_t)(ri.x >= 0 ? ri.x : 0) * (uint64_t)a.h + (uint64_t)(4 * pc);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = hres[q] + drop_apply(a.drop, i0 + q, o[q]);
+      }
     }
     const bool rok = ri.x >= 0 && pok;
     if (rok && (ABL & 64) == 0) {
@@ -552,10 +573,10 @@ __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, cons
     }
   }
   if constexpr (RTI + 1 < RT)
-    fk_epi_row<RTI + 1, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL>(st, a, x0, pc, pok, bj, carry, ccnt);
+    fk_epi_row<RTI + 1, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
 }
 
-template <int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, int PREC, int NW>
+template <int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC, int NW>
 __device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, const Args& a, const EpiCtx& x0, int i, int c,
                                            bool load_next, int i_next, int c_next) {
   const int ct = c * st.CTC + st.wave + NW * J;
@@ -574,7 +595,7 @@ __device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, cons
     }
     f32x4 carry = f32x4{0.f, 0.f, 0.f, 0.f};
     float ccnt = 0.f;
-    fk_epi_row<0, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL>(st, a, x0, pc, pok, bj, carry, ccnt);
+    fk_epi_row<0, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
   }
   // column tile J is stored: its accumulators start the next (tile, chunk) (after the last tile the
   // loads re-read this tile's rows and go unused)
@@ -586,10 +607,10 @@ __device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, cons
     for (int rt = 0; rt < RT; ++rt) st.acc[rt][J] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if constexpr (J + 1 < CT)
-    fk_epi_col<J + 1, RT, CT, AACT, SUMONLY, MAXL, GD, ABL>(st, a, x0, i, c, load_next, i_next, c_next);
+    fk_epi_col<J + 1, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
 }
 
-template <int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, int PREC, int NW>
+template <int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC, int NW>
 __device__ __forceinline__ void fk_epilogue(State<RT, CT, GD, PREC, NW>& st, const Args& a, int i, int c, int n,
                                             bool load_next, int i_next, int c_next) {
   EpiCtx x0;
@@ -598,7 +619,11 @@ __device__ __forceinline__ void fk_epilogue(State<RT, CT, GD, PREC, NW>& st, con
   x0.SO4 = reinterpret_cast<f32x4*>(a.SO);
   x0.em = st.emap + (i % kEmaps) * State<RT, CT, GD, PREC, NW>::ROWS;
   x0.n = n;
-  fk_epi_col<0, RT, CT, AACT, SUMONLY, MAXL, GD, ABL>(st, a, x0, i, c, load_next, i_next, c_next);
+  if constexpr (DROP) {
+    // the accumulators hold U alone: the residual rows are fetched next to the stores (fk_epi_row)
+    x0.H4 = (a.residual && a.H != nullptr) ? reinterpret_cast<const f32x4*>(a.H) : nullptr;
+  }
+  fk_epi_col<0, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
 }
 
 constexpr int kLbiasB = 512 * 4;  // the bias in LDS (4-wave workgroups, h <= 512)
@@ -613,9 +638,14 @@ __device__ __forceinline__ void fk_barrier() {
 // 64 no H_out stores, 128 no S_out stores; 256 (results valid): per-phase s_memtime cycle sums into
 // g_pk_stamps (0 residual scale + MFMAs, 1 W issue, 2 split + gather issue, 3 barrier, 4 epilogue,
 // 6 whole loop, 7 waves).
+// DROP: the update passes the dropout mask a.drop before the residual is added (fp32 only):
+// H_out = (residual ? H : 0) + keep U / (1 - p).  The accumulators then start at zero and hold U
+// alone, and the residual piece is loaded in the epilogue next to its store; max|H_out|, max|S_out|
+// and the aggregation are those of the values after dropout.
 template <int RT, int CT, int ACT, int AACT, bool SUMONLY, int MAXL, int GD = 2, int ABL = 0, int PREC = 0,
-          int NW = 8>
+          int NW = 8, bool DROP = false>
 __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
+  static_assert(!DROP || PREC == 0, "the dropout epilogue is fp32 only (bf16: update_bf16_kernel)");
   // fused variants (MAXL > 1) read their rows from the row table, plain ones from src / rev
   constexpr bool TABLE = MAXL > 1;
   using St = State<RT, CT, GD, PREC, NW>;
@@ -695,7 +725,7 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
     st.sAW = st.sA * sW;
     st.inv = 1.f / st.sAW;  // exact: a power of two
   }
-  const bool resid = (ABL & 32) == 0 && a.residual && a.H != nullptr;
+  const bool resid = !DROP && (ABL & 32) == 0 && a.residual && a.H != nullptr;  // residual rows into the accumulators
   const bool info_writer = st.g16 == 0 && st.wave < RT;
   const int SPT = a.nchunks * a.KS;  // steps per tile
 
@@ -826,7 +856,7 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
     const bool last_c = c + 1 == a.nchunks;
     const int i_next = last_c ? (i + 1 < ntl ? i + 1 : i) : i, c_next = last_c ? 0 : c + 1;
     if constexpr ((ABL & 8) == 0) {
-      fk_epilogue<RT, CT, AACT, SUMONLY, MAXL, GD, ABL>(st, a, i, c, n_cur, resid, i_next, c_next);
+      fk_epilogue<RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, i, c, n_cur, resid, i_next, c_next);
       stamp(4);
     }
     // (6) advance: tile i + 1 becomes current, tile i + 2's row (loaded a tile ago) is published

@@ -44,32 +44,40 @@ int xcd_count();  // update_ps.hip
 namespace nt {
 // ------------------------------------------------------------------------------ fk launcher
 namespace {
-template <int RT, int CT, int ACT, int AACT, bool SUMONLY, int MAXL>
+// DROP (every launcher below): the instance that passes the update through the dropout mask a.drop
+// (nt_dmpnn_update_fused_dropout; fused plans only)
+template <int RT, int CT, int ACT, int AACT, bool SUMONLY, int MAXL, bool DROP = false>
 int launch_fk_t(const fk::Args& a, int grid, hipStream_t stream) {
-  set_last_kernel(RT == 8 ? "update_fk_kernel: one 8-wave workgroup per CU, 128-row tiles"
-                          : "update_fk_kernel: one 8-wave workgroup per CU, 64-row tiles");
-  fk::update_fk_kernel<RT, CT, ACT, AACT, SUMONLY, MAXL><<<grid, fk::kThreads, 0, stream>>>(a);
+  if constexpr (DROP)
+    set_last_kernel(RT == 8 ? "update_fk_kernel: one 8-wave workgroup per CU, 128-row tiles, dropout in the epilogue"
+                            : "update_fk_kernel: one 8-wave workgroup per CU, 64-row tiles, dropout in the epilogue");
+  else
+    set_last_kernel(RT == 8 ? "update_fk_kernel: one 8-wave workgroup per CU, 128-row tiles"
+                            : "update_fk_kernel: one 8-wave workgroup per CU, 64-row tiles");
+  fk::update_fk_kernel<RT, CT, ACT, AACT, SUMONLY, MAXL, 2, 0, 0, 8, DROP><<<grid, fk::kThreads, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
 
 // 128-row tiles: relu layers with a sum aggregation whose act is relu / identity, or no aggregation
-template <int CT>
+template <int CT, bool DROP = false>
 int launch_fk_wide(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
-  const bool fused = a.SO != nullptr;
+  [[maybe_unused]] const bool fused = a.SO != nullptr;
   const bool relu = a.act == NT_ACT_RELU;
-  if (!fused) {  // plain update / dense mode: no aggregation
-    if (relu) return launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
-    if (a.act == NT_ACT_IDENTITY)
-      return launch_fk_t<8, CT, NT_ACT_IDENTITY, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
-    return launch_fk_t<8, CT, -1, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+  if constexpr (!DROP) {
+    if (!fused) {  // plain update / dense mode: no aggregation
+      if (relu) return launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+      if (a.act == NT_ACT_IDENTITY)
+        return launch_fk_t<8, CT, NT_ACT_IDENTITY, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+      return launch_fk_t<8, CT, -1, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+    }
   }
   // fused (fk_tile_rows: act = relu): scan rounds 3 cover in-degree <= 4 (molecules), 8 in-degree <= 9
   // (the non-hub nodes of hub graphs, cut at HUB_CUT_DEGREE), 16 every plan
 #ifdef NT_DIAG
   {  // per-phase stamps of the config-2 instance (tools/stamps_fk.py)
     const char* e = getenv("NT_FK_ABL");
-    if (e && atoi(e) == 256 && maxl <= 3 && a.aact == NT_ACT_RELU) {
+    if (!DROP && e && atoi(e) == 256 && maxl <= 3 && a.aact == NT_ACT_RELU) {
       fk::update_fk_kernel<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 3, 2, 256><<<grid, fk::kThreads, 0, stream>>>(a);
       NT_LAUNCH_CHECK();
       return NT_OK;
@@ -77,12 +85,12 @@ int launch_fk_wide(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
   }
 #endif
   if (a.aact == NT_ACT_RELU)
-    return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 3>(a, grid, stream)
-           : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 8>(a, grid, stream)
-                       : launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 16>(a, grid, stream);
-  return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 3>(a, grid, stream)
-         : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 8>(a, grid, stream)
-                     : launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 16>(a, grid, stream);
+    return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 3, DROP>(a, grid, stream)
+           : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 8, DROP>(a, grid, stream)
+                       : launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 16, DROP>(a, grid, stream);
+  return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 3, DROP>(a, grid, stream)
+         : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 8, DROP>(a, grid, stream)
+                     : launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 16, DROP>(a, grid, stream);
 }
 
 #ifdef NT_DIAG
@@ -170,22 +178,24 @@ bool fk_nw4(int64_t h, bool fused, int act, int reduce, int aact) {
 }
 bool fk_nw4_forced() { return fk_nw_env() == 4; }
 
-template <int AACT, int MAXL>
+template <int AACT, int MAXL, bool DROP>
 int launch_fk_nw4_t(const fk::Args& a, int grid, hipStream_t stream) {
-  set_last_kernel("update_fk_kernel: two 4-wave workgroups per CU, 64-row tiles");
-  fk::update_fk_kernel<4, 5, NT_ACT_RELU, AACT, true, MAXL, 2, 0, 0, 4><<<grid, 256, 0, stream>>>(a);
+  set_last_kernel(DROP ? "update_fk_kernel: two 4-wave workgroups per CU, 64-row tiles, dropout in the epilogue"
+                       : "update_fk_kernel: two 4-wave workgroups per CU, 64-row tiles");
+  fk::update_fk_kernel<4, 5, NT_ACT_RELU, AACT, true, MAXL, 2, 0, 0, 4, DROP><<<grid, 256, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
 
+template <bool DROP = false>
 int launch_fk_nw4(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
   if (a.aact == NT_ACT_RELU)
-    return maxl <= 3   ? launch_fk_nw4_t<NT_ACT_RELU, 3>(a, grid, stream)
-           : maxl <= 8 ? launch_fk_nw4_t<NT_ACT_RELU, 8>(a, grid, stream)
-                       : launch_fk_nw4_t<NT_ACT_RELU, 16>(a, grid, stream);
-  return maxl <= 3   ? launch_fk_nw4_t<NT_ACT_IDENTITY, 3>(a, grid, stream)
-         : maxl <= 8 ? launch_fk_nw4_t<NT_ACT_IDENTITY, 8>(a, grid, stream)
-                     : launch_fk_nw4_t<NT_ACT_IDENTITY, 16>(a, grid, stream);
+    return maxl <= 3   ? launch_fk_nw4_t<NT_ACT_RELU, 3, DROP>(a, grid, stream)
+           : maxl <= 8 ? launch_fk_nw4_t<NT_ACT_RELU, 8, DROP>(a, grid, stream)
+                       : launch_fk_nw4_t<NT_ACT_RELU, 16, DROP>(a, grid, stream);
+  return maxl <= 3   ? launch_fk_nw4_t<NT_ACT_IDENTITY, 3, DROP>(a, grid, stream)
+         : maxl <= 8 ? launch_fk_nw4_t<NT_ACT_IDENTITY, 8, DROP>(a, grid, stream)
+                     : launch_fk_nw4_t<NT_ACT_IDENTITY, 16, DROP>(a, grid, stream);
 }
 
 #ifdef NT_DIAG
@@ -239,23 +249,25 @@ int launch_fw(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
 #endif  // NT_DIAG
 
 // 64-row tiles: every other combination (any reduce, any aggregation act) and h > 384
-template <int CT>
+template <int CT, bool DROP = false>
 int launch_fk_narrow(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
   const bool fused = a.SO != nullptr;
   const bool relu = a.act == NT_ACT_RELU;
   const bool fast = !fused || (a.reduce == NT_SUM && (a.aact == NT_ACT_RELU || a.aact == NT_ACT_IDENTITY));
   if (fast) {
-    if (!fused)
-      return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 1>(a, grid, stream)
-                  : launch_fk_t<4, CT, -1, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+    if constexpr (!DROP) {
+      if (!fused)
+        return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 1>(a, grid, stream)
+                    : launch_fk_t<4, CT, -1, NT_ACT_IDENTITY, true, 1>(a, grid, stream);
+    }
     if (a.aact == NT_ACT_RELU)
-      return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_RELU, true, 16>(a, grid, stream)
-                  : launch_fk_t<4, CT, -1, NT_ACT_RELU, true, 16>(a, grid, stream);
-    return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 16>(a, grid, stream)
-                : launch_fk_t<4, CT, -1, NT_ACT_IDENTITY, true, 16>(a, grid, stream);
+      return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_RELU, true, 16, DROP>(a, grid, stream)
+                  : launch_fk_t<4, CT, -1, NT_ACT_RELU, true, 16, DROP>(a, grid, stream);
+    return relu ? launch_fk_t<4, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 16, DROP>(a, grid, stream)
+                : launch_fk_t<4, CT, -1, NT_ACT_IDENTITY, true, 16, DROP>(a, grid, stream);
   }
   (void)maxl;
-  return launch_fk_t<4, CT, -1, -1, false, 16>(a, grid, stream);
+  return launch_fk_t<4, CT, -1, -1, false, 16, DROP>(a, grid, stream);
 }
 }  // namespace
 
@@ -285,10 +297,12 @@ bool fw_active(int64_t h, int dtype, int act, int reduce, int aact) {
 
 int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in, float* amax_out,
                      const int32_t* tile_ptr, int64_t ntiles, int tile_rows, int max_in_degree,
-                     const void* row_table, int reduce, int aact, float aalpha, float* S_out) {
+                     const void* row_table, int reduce, int aact, float aalpha, float* S_out,
+                     const DropMask* drop) {
   const bool fused = tile_ptr != nullptr;
   NT_REQUIRE(fused == (S_out != nullptr), NT_EINVAL, "S_out must be given exactly with a tile plan");
   NT_REQUIRE(!fused || row_table, NT_EINVAL, "fp32 fused mode needs the row table (nt_dmpnn_row_table)");
+  NT_REQUIRE(drop == nullptr || fused, NT_EUNSUPPORTED, "the dropout layer kernel needs a tile plan");
   NT_REQUIRE(amax_in != nullptr, NT_EINVAL, "fp32 update needs amax_in (max|H|, max|S| on the device)");
   NT_REQUIRE(u.h % 4 == 0, NT_EUNSUPPORTED, "fp32 update needs h % 4 == 0");
   NT_REQUIRE((u.E * u.h) / 4 < (int64_t(1) << 31) && (u.V * u.h) / 4 < (int64_t(1) << 31),
@@ -342,6 +356,7 @@ int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in
   a.O = u.H_out;
   a.SO = S_out;
   a.SP = u.S_part;
+  if (drop) a.drop = *drop;
   a.nxcd = xcd_count();
   {
     // timing experiments only, read once per process: NT_FK_STAGGER (start delay of half the grid)
@@ -363,13 +378,13 @@ int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in
   const int grid = a.ntiles < cu_count() ? a.ntiles : cu_count();
   const int maxl = max_in_degree - 1;  // scan rounds needed within a 16-row tile
 #ifdef NT_DIAG
-  if (fk2_selected(u.h)) {
+  if (fk2_selected(u.h) && !drop) {
     a.nchunks = 1;
     return launch_fk2(a, grid, u.stream);
   }
 #endif
 #ifdef NT_DIAG
-  if (fused && fw_active(u.h, NT_F32, u.act, reduce, aact)) {
+  if (fused && !drop && fw_active(u.h, NT_F32, u.act, reduce, aact)) {
     a.nchunks = 1;
     return launch_fw(a, maxl, grid, u.stream);
   }
@@ -377,19 +392,19 @@ int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in
   if (fused && tile_rows <= 64 && fk_nw4(u.h, true, u.act, reduce, aact)) {
     a.nchunks = 1;
     const int g4 = a.ntiles < 2 * cu_count() ? a.ntiles : 2 * cu_count();
-    return launch_fk_nw4(a, maxl, g4, u.stream);
+    return drop ? launch_fk_nw4<true>(a, maxl, g4, u.stream) : launch_fk_nw4(a, maxl, g4, u.stream);
   }
   // up to 3 column tiles per wave (NT <= 24, one chunk); waves past NT skip theirs at run time
   if (cap == 128) {
     a.nchunks = 1;
-    return launch_fk_wide<3>(a, maxl, grid, u.stream);
+    return drop ? launch_fk_wide<3, true>(a, maxl, grid, u.stream) : launch_fk_wide<3>(a, maxl, grid, u.stream);
   }
   if (a.NT <= 24) {
     a.nchunks = 1;
-    return launch_fk_narrow<3>(a, maxl, grid, u.stream);
+    return drop ? launch_fk_narrow<3, true>(a, maxl, grid, u.stream) : launch_fk_narrow<3>(a, maxl, grid, u.stream);
   }
   a.nchunks = (a.NT + 31) / 32;
-  return launch_fk_narrow<4>(a, maxl, grid, u.stream);
+  return drop ? launch_fk_narrow<4, true>(a, maxl, grid, u.stream) : launch_fk_narrow<4>(a, maxl, grid, u.stream);
 }
 
 // ------------------------------------------------------------------------------ bf16 on the fk skeleton

@@ -864,9 +864,16 @@ def dmpnn_update_fused(
     pitch_out: int | None = None,
     S_part: Tensor | None = None,
     n_nodes: int | None = None,
+    dropout: tuple[float, int, int] | None = None,
 ) -> tuple[Tensor, Tensor | None]:
     """H_out = (residual ? H : 0) + (S[src] - act(H[rev])) @ W^T + b and, with a tile plan (tiles of at
     most ``tile_rows`` rows), S_out = scatter(agg_act(H_out), dst, reduce) in the same persistent launch.
+
+    ``dropout`` = (p, seed, offset) (with a plan only; nt_dmpnn_update_fused_dropout): the update passes
+    the mask of dropout_residual(p, seed, offset) before the residual is added,
+    H_out = (residual ? H : 0) + keep * ((S[src] - act(H[rev])) @ W^T + b) / (1 - p), in the layer
+    kernel's epilogue; S_out and amax_out are those of the values after dropout.  bf16: plans of at
+    most 64 rows.
 
     fp32: H and S may be row-padded views with one common pitch (see dmpnn_init's ``pitch``); H_out /
     S_out are allocated with rows ``pitch_out`` floats apart (default: dense), or given with one pitch.
@@ -881,6 +888,16 @@ def dmpnn_update_fused(
     ``n_nodes``: the aggregation's segment count, i.e. the rows S_out must hold (default: S's rows;
     the backward's fused dA passes S = G with E rows and S_out with the graph's V)."""
     dev = _require_device(H, S, src, rev, Wp, bias, out, S_out, perm, amax_in, amax_out)
+    if dropout is not None:
+        p, seed, offset = float(dropout[0]), int(dropout[1]), int(dropout[2])
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("dropout probability must be in [0, 1]")
+        if offset < 0:
+            raise ValueError("dropout offset must be >= 0")
+        if plan is None:
+            raise ValueError("dropout in the layer kernel needs a tile plan")
+        if H.dtype == torch.bfloat16 and tile_rows > 64:
+            raise ValueError("bf16 dropout in the layer kernel takes plans of at most 64 rows")
     ld_in = _row_pitch("H", H)
     code = _DTYPE_CODES[H.dtype]
     if _row_pitch("S", S, H.dtype) != ld_in:
@@ -937,12 +954,14 @@ def dmpnn_update_fused(
         absmax(H.contiguous(), amax_in[0:1])
         absmax(S.contiguous(), amax_in[1:2])
     lib = _lib.load()
-    _run(dev, lib.nt_dmpnn_update_fused,
-         _ptr(H), _ptr(S), _ptr(src), _ptr(rev), _ptr(Wp), _ptr(bias), V, E, h, int(residual),
-         act[0], act[1], _ptr(tile_ptr), ntiles, int(tile_rows), int(max_in_degree), _ptr(perm), _ptr(dsts),
-         _ptr(row_table), reduce_code(reduce), agg_act[0], agg_act[1], code, _ptr(amax_in), _ptr(amax_out),
-         _ptr(out), _ptr(S_out), _ptr(S_part), 0 if ld_in == h else ld_in, 0 if ld_out == h else ld_out,
-         _stream(dev))
+    args = (_ptr(H), _ptr(S), _ptr(src), _ptr(rev), _ptr(Wp), _ptr(bias), V, E, h, int(residual),
+            act[0], act[1], _ptr(tile_ptr), ntiles, int(tile_rows), int(max_in_degree), _ptr(perm), _ptr(dsts),
+            _ptr(row_table), reduce_code(reduce), agg_act[0], agg_act[1], code, _ptr(amax_in), _ptr(amax_out),
+            _ptr(out), _ptr(S_out), _ptr(S_part), 0 if ld_in == h else ld_in, 0 if ld_out == h else ld_out)
+    if dropout is not None:
+        _run(dev, lib.nt_dmpnn_update_fused_dropout, *args, p, seed & (2**64 - 1), offset, _stream(dev))
+    else:
+        _run(dev, lib.nt_dmpnn_update_fused, *args, _stream(dev))
     return out, S_out
 
 

@@ -11,10 +11,14 @@ Forward (per call, all on ``torch.cuda.current_stream()``, inputs already reside
                              S = scatter(act(H_{l+1}), dst)   (last layer: node = scatter(H_d, dst),
                                                                chemprop.py:86)
 
-d + 1 launches (+ one nt_dmpnn_pack_weights_fk launch pair per new set of weights).  Otherwise
-(dropout, or no fused plan):
+d + 1 launches (+ one nt_dmpnn_pack_weights_fk launch pair per new set of weights).  Training-mode
+dropout keeps that sequence: nt_dmpnn_update_fused_dropout applies layer l's mask (p, seed,
+dropout_offset(l, E, h)) to the update in the layer kernel's epilogue, ahead of the residual add and
+the aggregation (NT_FUSED_DROPOUT=0, or bf16 above BF16_FUSED_DROPOUT_MAX_H: the unfused sequence
+below).  Otherwise (no fused plan):
 
     nt_dmpnn_init; for l: nt_dmpnn_update, nt_segment_reduce; nt_segment_reduce (node)   2 + 2d launches
+      (dropout: nt_dmpnn_update without its residual, then nt_dropout_residual adds it back)
 
 bf16 features (BASELINE config 3) run the same d + 1 launch sequence on the bf16 kernels
 (csrc/bf16.hip: the 64-edge-tile update fused with the next aggregation).  Activations without a
@@ -76,6 +80,11 @@ BF16_WGRAD_MAX_H = 2048
 # kernel as before.  Measured: 2.3 to 3.6 times faster than the bf16x6 kernel at 384,
 # 512, 1024, 2048 and 4096, the training step 23 % to 40 % shorter; 4096 is the largest size measured.
 FP32_WGRAD_FK_MAX_H = 4096
+# bf16 dropout in the fused layer launch: the largest h _layers_forward sends to
+# nt_dmpnn_update_fused_dropout (the entry accepts every bf16 h the plain one does).  Measured faster at
+# h = 512; above it the column-pass kernel's dropout epilogue is tested at kernel level
+# but not timed, so those blocks keep the unfused update + nt_dropout_residual + segment reduce.
+BF16_FUSED_DROPOUT_MAX_H = 512
 
 # Optional per-launch timer for the dominant kernel (bench.py sets it): a list that receives
 # (start, end) torch.cuda.Event pairs recorded on the launch stream around every nt_dmpnn_update.
@@ -308,6 +317,13 @@ def _aggregate(X, seg_ptr, perm, nseg, reduce, act, chunks, out=None, amax=None)
 
 def _fused_enabled() -> bool:
     return os.environ.get("NT_FUSED", "1") != "0"
+
+
+def _fused_dropout_enabled() -> bool:
+    """Training-mode dropout inside the fused layer launch (nt_dmpnn_update_fused_dropout): fp32, and
+    bf16 up to BF16_FUSED_DROPOUT_MAX_H (both measured faster); NT_FUSED_DROPOUT=0 (A/B)
+    keeps the unfused update + nt_dropout_residual + segment reduce."""
+    return os.environ.get("NT_FUSED_DROPOUT", "1") != "0"
 
 
 # ------------------------------------------------------------------------------------ forward
@@ -656,10 +672,12 @@ def embed_init_mixed(node_table, node_types, edge_table, edge_types, src, lay, n
 
 def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residual, keep_states, drop=None,
                     amax=None):
-    """The d layers + final node scatter, from H0 and layer 0's aggregation S.  With dropout the
-    update runs without its residual and nt_dropout_residual adds it back (the fused and persistent
-    kernels write H_out directly, so dropout takes the unfused update).  amax (fp32): the split
-    scales, row 0 filled by the init (see _amax_buffer)."""
+    """The d layers + final node scatter, from H0 and layer 0's aggregation S.  drop = (p, seed):
+    training-mode dropout of every layer's update.  On a graph with a fused plan the layer kernel
+    applies the mask in its epilogue (nt_dmpnn_update_fused_dropout, one launch per layer, the fp32
+    amax chain kept); without a plan, in bf16 above BF16_FUSED_DROPOUT_MAX_H, or with NT_FUSED_DROPOUT=0,
+    the update runs without its residual and nt_dropout_residual adds it back.  amax (fp32): the split scales, row 0 filled by the init
+    (see _amax_buffer)."""
     d = len(weights)
     chunks = dst_chunks(lay)
     if d == 0:
@@ -680,17 +698,23 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
         amax = _amax_buffer(d, H)
         K.absmax(H, amax[0, 0:1])
         K.absmax(S, amax[0, 1:2])
-    fusable = drop is None and _fused_enabled() and K.fused_supported(V, E, h, H.dtype)
+    drop_fusable = drop is None or (_fused_dropout_enabled() and (fp32 or h <= BF16_FUSED_DROPOUT_MAX_H))
+    fusable = drop_fusable and _fused_enabled() and K.fused_supported(V, E, h, H.dtype)
     rows = 64
     if fusable:  # the layer kernel's tile capacity for every layer of this block
         rows = min(K.fused_tile_rows(h, H.dtype, act, reduce, act),
                    K.fused_tile_rows(h, H.dtype, act, reduce, _IDENTITY))
         if rows == 128 and fp32 and h <= 320 and E <= NW4_MAX_EDGES and os.environ.get("NT_FK_NW") != "8":
             rows = 64  # the two-workgroups-per-CU walk of 64-row tiles (update_pk.hip, fk_nw4)
+        if drop is not None and not fp32:
+            rows = 64  # bf16 dropout lives in the 64-row kernel's epilogue, whatever NT_BF16_KERNEL selects
     plan = fused_plan(lay, V, E, rows, H.dtype) if fusable else None
     if plan is not None:
         return _fused_forward(H, S, src, rev, lay, plan, rows, Wps, biases, act, reduce, residual, keep_states,
-                              amax)
+                              amax, drop)
+    # no plan (or dropout kept off the fused launch): layer by layer; with dropout the fp32 layers take
+    # the plain update kernel, not the persistent one
+    fusable = fusable and drop is None
     if not H.is_contiguous():  # row-padded init output (row_pitch) on a graph the fused plan cannot take
         H, S = H.contiguous(), S.contiguous()
     states = []
@@ -775,8 +799,12 @@ def hub_run_table(lay: DeviceLayout, rt: Tensor, tile_ptr: Tensor, dsts: Tensor,
     return hit[1]
 
 
-def _fused_forward(H, S, src, rev, lay, plan, rows, Wps, biases, act, reduce, residual, keep_states, amax):
+def _fused_forward(H, S, src, rev, lay, plan, rows, Wps, biases, act, reduce, residual, keep_states, amax,
+                   drop=None):
+    """One launch per layer over the fused plan; drop = (p, seed): layer l's update passes the dropout
+    mask of (p, seed, dropout_offset(l, E, h)) in the same launch."""
     tile_ptr, ntiles, dsts, zero_fill = plan
+    E, h = H.shape
     # zero fills only where a row is read or returned (zero_rows_needed): the last layer's node output;
     # an intermediate S only if some source node has no in-edge
     zf_out, zf_mid, _ = zero_rows_needed(lay, src, S.shape[0]) if zero_fill else (False, False, False)
@@ -811,6 +839,7 @@ def _fused_forward(H, S, src, rev, lay, plan, rows, Wps, biases, act, reduce, re
             amax_in=None if amax is None else amax[l],
             amax_out=None if (amax is None or last) else amax[l + 1],  # row d has no reader
             row_table=rt, out=spare_H, S_out=None if last else spare_S, pitch_out=pitch, S_part=part,
+            dropout=None if drop is None else (drop[0], drop[1], dropout_offset(l, E, h)),
         )
         if timer is not None:
             ev[1].record()

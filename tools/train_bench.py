@@ -15,11 +15,17 @@ nt_embed_bag_backward for the tables); --embed-bwd torch is the library path tha
 --autocast (with --dtype f32) is mixed precision as Lightning's precision="bf16-mixed" runs it: the
 module, its gradients and the Adam state stay fp32, and the forward and the loss of every step run
 inside torch.autocast("cuda", dtype=torch.bfloat16), so the block computes on the bf16 kernels.
+--dropout P trains with nn.Dropout(P) in every layer's update (the fwd row is then a train()-mode
+forward under no_grad: it drops too).  By default the layer kernel applies the mask in its epilogue
+(nt_dmpnn_update_fused_dropout); NT_FUSED_DROPOUT=0 in the environment is the A/B: the unfused update,
+nt_dropout_residual and a separate segment reduce.  With --dropout the JSON also carries the layer
+launch the forward took and its median time (the engine's event pair around every layer launch: on
+the unfused path it spans the update and the dropout kernel, not the segment reduce that follows).
 The table and the JSON also report torch.cuda.max_memory_allocated over the timed steps.
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
                                   [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--autocast]
-                                  [--json]"""
+                                  [--dropout P] [--json]"""
 import argparse
 import contextlib
 import json
@@ -61,6 +67,9 @@ def main():
     p.add_argument("--autocast", action="store_true",
                    help="fp32 module (--dtype f32) with the forward and the loss of every step inside "
                         "torch.autocast('cuda', dtype=torch.bfloat16): fp32 master weights, bf16 kernels")
+    p.add_argument("--dropout", type=float, default=0.0,
+                   help="dropout probability of every layer's update (training mode; NT_FUSED_DROPOUT=0 keeps "
+                        "it off the fused layer launch)")
     p.add_argument("--json", action="store_true", help="print one JSON object instead of the table")
     a = p.parse_args()
     if a.autocast and a.dtype != "f32":
@@ -79,7 +88,7 @@ def main():
     if a.embedded:
         os.environ["NT_EMBED_BWD"] = a.embed_bwd
         Gd = G.to("cuda")  # node_feats / edge_feats stay the integer type columns
-        blk = EmbeddedChempropBlock(GraphEmbedding(42, 13, a.h), ChempropBlock(a.h, depth=a.depth))
+        blk = EmbeddedChempropBlock(GraphEmbedding(42, 13, a.h), ChempropBlock(a.h, depth=a.depth, dropout=a.dropout))
         blk = blk.to("cuda", dt).train()
     else:
         ev = torch.nn.EmbeddingBag(42, a.h, mode="sum")
@@ -87,7 +96,7 @@ def main():
         with torch.no_grad():
             Xv, Xe = ev(G.node_feats).to(dt), ee(G.edge_feats).to(dt)
         Gd = G.update(node_feats=Xv, edge_feats=Xe).to("cuda")
-        blk = ChempropBlock(a.h, depth=a.depth).to("cuda", dt).train()
+        blk = ChempropBlock(a.h, depth=a.depth, dropout=a.dropout).to("cuda", dt).train()
         Xv_d = Gd.node_feats.requires_grad_(True)
         Xe_d = Gd.edge_feats.requires_grad_(True)
     opt = None
@@ -139,19 +148,33 @@ def main():
                 ts.append(s.elapsed_time(e) / chunk)
             res[name] = statistics.median(ts)
             mem[name] = torch.cuda.max_memory_allocated()
+    layer = {}
+    if a.dropout > 0:  # which layer launch the forward takes, and its median time
+        from notorch_amd.nn.gnn import _engine
+
+        _engine.UPDATE_EVENTS = evs = []
+        for _ in range(10):
+            fwd()
+        torch.cuda.synchronize()
+        _engine.UPDATE_EVENTS = None
+        layer = {"dropout": a.dropout, "fused_dropout": os.environ.get("NT_FUSED_DROPOUT", "1") != "0",
+                 "layer_kernel": _engine.LAST_UPDATE_INFO.get("kernel"),
+                 "layer_us": statistics.median(s.elapsed_time(e) for s, e in evs) * 1e3}
     if a.json:
         print(json.dumps({
             "V": G.num_nodes, "E": E, "h": a.h, "depth": a.depth, "dtype": a.dtype,
             "weight_grad": os.environ.get("NT_WGRAD", "default"), "optim": a.optim,
             **({"embedded": True, "embed_bwd": a.embed_bwd} if a.embedded else {}),
             **({"autocast": "bf16"} if a.autocast else {}),
+            **layer,
             "max_memory_allocated": mem,
             "warmup": a.warmup, "steps": a.steps,
             "ms": res, "edge_messages_per_s": {k: E * a.depth / (v * 1e-3) for k, v in res.items()},
         }), flush=True)
         return
     print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}"
-          + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else "") + (" autocast=bf16" if a.autocast else ""))
+          + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else "") + (" autocast=bf16" if a.autocast else "")
+          + (f" dropout={a.dropout} layer {layer['layer_us']:.1f} us: {layer['layer_kernel']}" if layer else ""))
     for k, v in res.items():
         print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s  "
               f"max allocated {mem[k] / 2**20:.1f} MiB")
