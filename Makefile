@@ -3,21 +3,13 @@ HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 SRC_DIR := notorch_amd/csrc
 SRCS    := $(wildcard $(SRC_DIR)/*.hip)
-HDRS    := $(wildcard $(SRC_DIR)/*.hpp) $(wildcard $(SRC_DIR)/diag/*.hpp) include/notorch_amd.h include/notorch_amd_train.h
+HDRS    := $(wildcard $(SRC_DIR)/*.hpp) include/notorch_amd.h include/notorch_amd_train.h
 FLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result \
            -fvisibility=hidden -DNT_BUILD
-# DIAG=1: the diagnostic library (A/B kernel variants, ablation and stamp builds selected by NT_*
-# environment variables) next to the shipping one; notorch_amd._lib loads it when NT_LIB=diag.
 # VARIANT=<name> EXTRA=-D...: an A/B build of the shipping sources into lib/libnotorch_amd_<name>.so
 # (loaded with NT_LIB=variant:<name>; experiments only, git- and gpurun-ignored build dirs)
 FLAGS   += $(EXTRA)
-ifeq ($(DIAG),1)
-OUT     := notorch_amd/lib/libnotorch_amd_diag.so
-BDIR    := build_diag
-FLAGS   += -DNT_DIAG
-# csrc/diag/: kernels of the diagnostic library only (A/B variants superseded in the shipping one)
-SRCS    += $(wildcard $(SRC_DIR)/diag/*.hip)
-else ifneq ($(VARIANT),)
+ifneq ($(VARIANT),)
 OUT     := notorch_amd/lib/libnotorch_amd_$(VARIANT).so
 BDIR    := build_$(VARIANT)
 else
@@ -25,7 +17,6 @@ OUT     := notorch_amd/lib/libnotorch_amd.so
 BDIR    := build
 endif
 OBJS    := $(patsubst $(SRC_DIR)/%.hip,$(BDIR)/%.o,$(SRCS))
-DIAG_OBJS := $(filter $(BDIR)/diag/%,$(OBJS))
 
 # host-only CPython helper of the native collate (csrc/host/collate_py.cpp): g++ against torch's headers
 PY      ?= python3
@@ -35,7 +26,7 @@ TORCH_FLAGS = $(shell $(PY) -c "import sysconfig, os, torch, torch.utils.cpp_ext
   '-D_GLIBCXX_USE_CXX11_ABI=%d' % int(torch._C._GLIBCXX_USE_CXX11_ABI), \
   '-L' + os.path.join(os.path.dirname(torch.__file__), 'lib'))")
 
-ifeq ($(DIAG)$(VARIANT),)
+ifeq ($(VARIANT),)
 all: $(OUT) $(PYEXT)
 else
 all: $(OUT)
@@ -58,6 +49,6 @@ resource-usage: $(SRCS)
 	@for f in $(SRCS); do $(HIPCC) $(FLAGS) -c $$f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs|LDS Size|Occupancy|SGPRs:"; done
 
 clean:
-	rm -rf build build_diag notorch_amd/lib/libnotorch_amd.so notorch_amd/lib/libnotorch_amd_diag.so $(PYEXT)
+	rm -rf build notorch_amd/lib/libnotorch_amd.so $(PYEXT)
 
 .PHONY: all clean resource-usage

@@ -25,8 +25,8 @@
 
 namespace nt {
 
-int cu_count();   // update_ps.hip
-int xcd_count();  // update_ps.hip
+int cu_count();   // tile_plan.hip
+int xcd_count();  // tile_plan.hip
 
 namespace {
 
@@ -181,11 +181,6 @@ __global__ void __launch_bounds__(256) pack_bf16(const bf16_t* __restrict__ W, i
 }
 
 // ------------------------------------------------------------------------------ update
-// BF_ABL (variant builds only, tools/r5_bf16_abl.sh): 1 = gathers read row 0, 2 = W fragments of
-// k step 0 only, 4 = no H' / S' stores, 8 = no residual loads, 16 = no MFMA.  Results are wrong.
-#ifndef BF_ABL
-#define BF_ABL 0
-#endif
 constexpr int kM = 64;        // edges per tile
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kNWMax = 8;     // column tiles per wave at h = 512 (NW = ceil(ceil(h/16) / 4))
@@ -286,7 +281,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
     cs = (s >= 0 && s < V) ? (int)s : -1;
     cq = (q >= 0 && q < E) ? (int)q : -1;
   };
-  // XCD-aware walk (as update_pk.hip): blocks b and b + nxcd share an XCD; each XCD takes one
+  // XCD-aware walk (as update_fk.hip): blocks b and b + nxcd share an XCD; each XCD takes one
   // contiguous 1/nxcd of the tiles, so rows shared by neighbouring tiles stay in its L2.
   int t_first = blockIdx.x, t_step = G, t_end = ntiles;
   if (nxcd > 1 && G % nxcd == 0) {
@@ -341,7 +336,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
       uint4 sraw[kRG], qraw[kRG];
 #pragma unroll
       for (int u = 0; u < kRG; ++u) {
-        const int64_t so = (BF_ABL & 1) ? 0 : soff[r0 + u], qo = (BF_ABL & 1) ? 0 : qoff[r0 + u];
+        const int64_t so = soff[r0 + u], qo = qoff[r0 + u];
         sraw[u] = *reinterpret_cast<const uint4*>(S + (so >= 0 ? so : 0) + kc);
         qraw[u] = *reinterpret_cast<const uint4*>(H + (qo >= 0 ? qo : 0) + kc);
       }
@@ -403,7 +398,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
   const char* arow = lds + (lane & 15) * lda + 16 * (lane >> 4);
   for (int ks = 0; ks < KS; ++ks) {
     // next step's fragments (the last step re-reads its own: no branch, no drain)
-    const int64_t kn = (BF_ABL & 2) ? 0 : (ks + 1 < KS ? ks + 1 : ks) * kstride;
+    const int64_t kn = (ks + 1 < KS ? ks + 1 : ks) * kstride;
     uint4 bnext[NW];
 #pragma unroll
     for (int j = 0; j < NW; ++j) bnext[j] = Wp[kn + boff(j)];
@@ -416,11 +411,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
       const bf16x8 b = __builtin_bit_cast(bf16x8, bcur[j]);
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) {
-        if constexpr ((BF_ABL & 16) != 0) {
-          acc[mt][j][0] += (float)a[mt][0] * (float)b[0];
-        } else {
-          acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b, acc[mt][j], 0, 0, 0);
-        }
+        acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt], b, acc[mt][j], 0, 0, 0);
       }
     }
 #pragma unroll
@@ -448,7 +439,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
     constexpr int kPre = kIt;
     auto load_res = [&](int it) {
       const int64_t e = erow[(tid >> 5) + 8 * it];
-      const bool ok = cok && e >= 0 && residual && (BF_ABL & 8) == 0;
+      const bool ok = cok && e >= 0 && residual;
       return *reinterpret_cast<const uint4*>(H + (ok ? e * h + n0 + cpiece : 0));
     };
     uint4 hres[kPre];
@@ -488,7 +479,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
             if constexpr (DROP) u = drop_apply(drop, (uint64_t)(e * h + n0 + cpiece + q), u);
             y[q] = u + (residual ? __uint_as_float(hb) : 0.f);
           }
-          if constexpr ((BF_ABL & 4) == 0) store_chunk<8>(out + e * h + n0 + cpiece, y);
+          store_chunk<8>(out + e * h + n0 + cpiece, y);
           if constexpr (AGG != 0) {  // the aggregation reads the stored (bf16) value, as unfused
 #pragma unroll
             for (int q = 0; q < 8; ++q) st[q] = AGG == 2 ? act_t<ACT>(rbf(y[q]), act, alpha) : rbf(y[q]);
@@ -506,7 +497,7 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
             case NT_MAX: reduce_rows<NT_MAX>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
             default: reduce_rows<NT_MIN>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
           }
-          if constexpr ((BF_ABL & 4) == 0) store_chunk<8>(agg.S_out + (int64_t)nnode[k] * h + n0 + cpiece, y);
+          store_chunk<8>(agg.S_out + (int64_t)nnode[k] * h + n0 + cpiece, y);
         }
       }
     } else {

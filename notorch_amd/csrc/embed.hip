@@ -18,11 +18,11 @@
 #include "rows.hpp"
 
 namespace nt {
-int fk_absmax(const float* X, int64_t n, float* out, hipStream_t stream);  // update_pk.hip
+int fk_absmax(const float* X, int64_t n, float* out, hipStream_t stream);  // update_fk.hip
 }
 
 namespace nt {
-int cu_count();  // update_ps.hip
+int cu_count();  // tile_plan.hip
 
 namespace {
 

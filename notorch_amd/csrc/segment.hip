@@ -406,7 +406,7 @@ extern "C" int nt_dmpnn_aggregate(const void* H, const int32_t* row_ptr, const i
 }
 
 namespace nt {
-int fk_absmax(const float* X, int64_t n, float* out, hipStream_t stream);  // update_pk.hip
+int fk_absmax(const float* X, int64_t n, float* out, hipStream_t stream);  // update_fk.hip
 }
 
 extern "C" int nt_dmpnn_init(const void* Xv, const void* Xe, const int64_t* src,

@@ -1,8 +1,6 @@
 // Tile planner of the fused layer kernels: node-aligned tiles of the dst-sorted edge order
 // (nt_dmpnn_tile_plan, nt_dmpnn_tile_plan_hubs), their balanced stride (nt_dmpnn_tile_stride), and the
-// device's CU / XCD counts the launchers size their grids by.  (The persistent producer/consumer "ps"
-// layer kernel that used to live here is an A/B variant of the diagnostic library:
-// csrc/diag/update_ps_ring.hip.)
+// device's CU / XCD counts (cu_count, xcd_count) the launchers size their grids by.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -73,8 +71,6 @@ int cu_count() {
   }
   return n[dev];
 }
-
-bool ps_supported(int64_t h) { return h % 4 == 0 && h >= 4 && h <= 304; }
 
 }  // namespace nt
 

@@ -6,9 +6,11 @@
 //   S_out[v] = reduce_{e: dst[e] = v} aact(H_out[e])                               (chemprop.py:37-39,
 //                                                                                 :86 with identity)
 //
-// The persistent K-slice-ring ("pk") kernel that used to live here is an A/B variant of the diagnostic
-// library: csrc/diag/update_pk_ring.hip.
-// Supports h % 4 == 0, h <= 304, E * h / 4 < 2^31, V * h / 4 < 2^31.
+// This file holds the host side of update_fk.hpp: the choice of kernel instance and grid per layer
+// (launch_update_fk for fp32, launch_update_fk_bf16 for bf16 storage), the tile capacity the plan
+// builders ask for (fk_tile_rows), and the launches of the image pack, row table and max|X| kernels.
+// fp32 supports h % 4 == 0, h <= 8192 (column chunks above 384), E * ld / 4 < 2^31, V * ld / 4 < 2^31;
+// bf16 h % 8 == 0, h <= 512.
 #include <stdlib.h>
 
 #include <atomic>
@@ -18,28 +20,13 @@
 #include "common.hpp"
 #include "update.hpp"
 
-namespace nt {
-
-#ifdef NT_DIAG
-// diagnostic builds only (the shipping library holds no device state): stamp sums of the fk (ABL 256)
-// and fw (FW_STAMP) walks, read by nt_debug_fw_stamps
-__device__ unsigned long long g_pk_stamps[10];
-#endif
-
-}  // namespace nt
-
 // the fp32 layer kernel (two-part fp16 split)
 #include "update_fk.hpp"
-#ifdef NT_DIAG
-#include "diag/update_fk2.hpp"  // A/B: LDS-staged output variant (NT_FK=2)
-#include "diag/update_fw.hpp"   // A/B: one-wave-per-SIMD walk of the fused layer (NT_FK_FW=1)
-#endif
 
 namespace nt {
-int cu_count();   // update_ps.hip
-int xcd_count();  // update_ps.hip
+int cu_count();   // tile_plan.hip
+int xcd_count();  // tile_plan.hip
 }  // namespace nt
-
 
 namespace nt {
 // ------------------------------------------------------------------------------ fk launcher
@@ -54,7 +41,7 @@ int launch_fk_t(const fk::Args& a, int grid, hipStream_t stream) {
   else
     set_last_kernel(RT == 8 ? "update_fk_kernel: one 8-wave workgroup per CU, 128-row tiles"
                             : "update_fk_kernel: one 8-wave workgroup per CU, 64-row tiles");
-  fk::update_fk_kernel<RT, CT, ACT, AACT, SUMONLY, MAXL, 2, 0, 0, 8, DROP><<<grid, fk::kThreads, 0, stream>>>(a);
+  fk::update_fk_kernel<RT, CT, ACT, AACT, SUMONLY, MAXL, 0, 8, DROP><<<grid, fk::kThreads, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -74,16 +61,6 @@ int launch_fk_wide(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
   }
   // fused (fk_tile_rows: act = relu): scan rounds 3 cover in-degree <= 4 (molecules), 8 in-degree <= 9
   // (the non-hub nodes of hub graphs, cut at HUB_CUT_DEGREE), 16 every plan
-#ifdef NT_DIAG
-  {  // per-phase stamps of the config-2 instance (tools/stamps_fk.py)
-    const char* e = getenv("NT_FK_ABL");
-    if (!DROP && e && atoi(e) == 256 && maxl <= 3 && a.aact == NT_ACT_RELU) {
-      fk::update_fk_kernel<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 3, 2, 256><<<grid, fk::kThreads, 0, stream>>>(a);
-      NT_LAUNCH_CHECK();
-      return NT_OK;
-    }
-  }
-#endif
   if (a.aact == NT_ACT_RELU)
     return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 3, DROP>(a, grid, stream)
            : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_RELU, true, 8, DROP>(a, grid, stream)
@@ -91,71 +68,6 @@ int launch_fk_wide(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
   return maxl <= 3   ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 3, DROP>(a, grid, stream)
          : maxl <= 8 ? launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 8, DROP>(a, grid, stream)
                      : launch_fk_t<8, CT, NT_ACT_RELU, NT_ACT_IDENTITY, true, 16, DROP>(a, grid, stream);
-}
-
-#ifdef NT_DIAG
-// fk2 (64-row tiles, output staged in LDS and written during the next tile): h <= 384, any layer
-template <int ACT, int AACT, bool SUMONLY, bool TABLE>
-int launch_fk2_t(const fk::Args& a, int grid, hipStream_t stream) {
-  fk::update_fk2_kernel<3, ACT, AACT, SUMONLY, TABLE><<<grid, fk::kThreads, 0, stream>>>(a);
-  NT_LAUNCH_CHECK();
-  return NT_OK;
-}
-
-int launch_fk2(const fk::Args& a, int grid, hipStream_t stream) {
-  const bool relu = a.act == NT_ACT_RELU, ident = a.act == NT_ACT_IDENTITY;
-  if (a.SO == nullptr) {  // plain / dense: no aggregation
-    if (relu) return launch_fk2_t<NT_ACT_RELU, NT_ACT_IDENTITY, true, false>(a, grid, stream);
-    if (ident) return launch_fk2_t<NT_ACT_IDENTITY, NT_ACT_IDENTITY, true, false>(a, grid, stream);
-    return launch_fk2_t<-1, NT_ACT_IDENTITY, true, false>(a, grid, stream);
-  }
-  const bool sum = a.reduce == NT_SUM;
-#ifdef NT_DIAG
-  if (relu && sum && a.aact == NT_ACT_RELU) {
-    const char* e = getenv("NT_FK_ABL");
-    switch (e ? atoi(e) : 0) {
-#define NT_FK2_ABL_CASE(n)                                                                                  \
-  case n:                                                                                                   \
-    fk::update_fk2_kernel<3, NT_ACT_RELU, NT_ACT_RELU, true, true, 2, n><<<grid, fk::kThreads, 0, stream>>>(a); \
-    NT_LAUNCH_CHECK();                                                                                      \
-    return NT_OK;
-      NT_FK2_ABL_CASE(1)
-      NT_FK2_ABL_CASE(2)
-      NT_FK2_ABL_CASE(6)
-      NT_FK2_ABL_CASE(8)
-      NT_FK2_ABL_CASE(16)
-      NT_FK2_ABL_CASE(32)
-      NT_FK2_ABL_CASE(64)
-      NT_FK2_ABL_CASE(70)
-      NT_FK2_ABL_CASE(102)
-      NT_FK2_ABL_CASE(71)
-      NT_FK2_ABL_CASE(24)
-      NT_FK2_ABL_CASE(128)
-      NT_FK2_ABL_CASE(198)
-#undef NT_FK2_ABL_CASE
-      default:
-        break;
-    }
-  }
-#endif
-  if (relu && sum && a.aact == NT_ACT_RELU) return launch_fk2_t<NT_ACT_RELU, NT_ACT_RELU, true, true>(a, grid, stream);
-  if (relu && sum && a.aact == NT_ACT_IDENTITY)
-    return launch_fk2_t<NT_ACT_RELU, NT_ACT_IDENTITY, true, true>(a, grid, stream);
-  return launch_fk2_t<-1, -1, false, true>(a, grid, stream);
-}
-
-#endif  // NT_DIAG
-
-// which fp32 layer kernel runs: update_fk_kernel; diagnostic builds: NT_FK=2 selects the LDS-staged
-// update_fk2_kernel for h <= 384
-bool fk2_selected(int64_t h) {
-#ifdef NT_DIAG
-  const char* e = getenv("NT_FK");
-  return e && e[0] == '2' && h <= fk::kFk2MaxH;
-#else
-  (void)h;
-  return false;
-#endif
 }
 
 // Fused relu / sum layers given a plan of <= 64-row tiles (h <= 320): two independent 4-wave
@@ -182,7 +94,7 @@ template <int AACT, int MAXL, bool DROP>
 int launch_fk_nw4_t(const fk::Args& a, int grid, hipStream_t stream) {
   set_last_kernel(DROP ? "update_fk_kernel: two 4-wave workgroups per CU, 64-row tiles, dropout in the epilogue"
                        : "update_fk_kernel: two 4-wave workgroups per CU, 64-row tiles");
-  fk::update_fk_kernel<4, 5, NT_ACT_RELU, AACT, true, MAXL, 2, 0, 0, 4, DROP><<<grid, 256, 0, stream>>>(a);
+  fk::update_fk_kernel<4, 5, NT_ACT_RELU, AACT, true, MAXL, 0, 4, DROP><<<grid, 256, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -197,56 +109,6 @@ int launch_fk_nw4(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
          : maxl <= 8 ? launch_fk_nw4_t<NT_ACT_IDENTITY, 8, DROP>(a, grid, stream)
                      : launch_fk_nw4_t<NT_ACT_IDENTITY, 16, DROP>(a, grid, stream);
 }
-
-#ifdef NT_DIAG
-// A/B switch: NT_FK_FW=1 / 0 (read once per process) selects update_fw_kernel where it applies;
-// nt_debug_set_fw overrides it (tests and kernel benches switch within one process)
-int g_fw_override = -1;
-bool fw_selected() {
-  static const int v = [] {
-    const char* e = getenv("NT_FK_FW");
-    return e && e[0] == '1' ? 1 : 0;
-  }();
-  return (g_fw_override >= 0 ? g_fw_override : v) != 0;
-}
-
-template <int AACT, int MAXL>
-int launch_fw_t(const fk::Args& a, int grid, hipStream_t stream) {
-  set_last_kernel("update_fw_kernel: one 4-wave workgroup per CU (one wave per SIMD), 128-row tiles");
-  fw::update_fw_kernel<5, 0, NT_ACT_RELU, AACT, MAXL><<<grid, fw::kThreads, 0, stream>>>(a);
-  NT_LAUNCH_CHECK();
-  return NT_OK;
-}
-
-template <int AACT, int MAXL>
-int launch_fwb_t(const fk::Args& a, int grid, hipStream_t stream) {
-  set_last_kernel("update_fw_kernel (bf16): one 4-wave workgroup per CU (one wave per SIMD), 128-row tiles");
-  fw::update_fw_kernel<8, 1, NT_ACT_RELU, AACT, MAXL><<<grid, fw::kThreads, 0, stream>>>(a);
-  NT_LAUNCH_CHECK();
-  return NT_OK;
-}
-
-int launch_fwb(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
-  if (a.aact == NT_ACT_RELU)
-    return maxl <= 3   ? launch_fwb_t<NT_ACT_RELU, 3>(a, grid, stream)
-           : maxl <= 8 ? launch_fwb_t<NT_ACT_RELU, 8>(a, grid, stream)
-                       : launch_fwb_t<NT_ACT_RELU, 16>(a, grid, stream);
-  return maxl <= 3   ? launch_fwb_t<NT_ACT_IDENTITY, 3>(a, grid, stream)
-         : maxl <= 8 ? launch_fwb_t<NT_ACT_IDENTITY, 8>(a, grid, stream)
-                     : launch_fwb_t<NT_ACT_IDENTITY, 16>(a, grid, stream);
-}
-
-int launch_fw(const fk::Args& a, int maxl, int grid, hipStream_t stream) {
-  if (a.aact == NT_ACT_RELU)
-    return maxl <= 3   ? launch_fw_t<NT_ACT_RELU, 3>(a, grid, stream)
-           : maxl <= 8 ? launch_fw_t<NT_ACT_RELU, 8>(a, grid, stream)
-                       : launch_fw_t<NT_ACT_RELU, 16>(a, grid, stream);
-  return maxl <= 3   ? launch_fw_t<NT_ACT_IDENTITY, 3>(a, grid, stream)
-         : maxl <= 8 ? launch_fw_t<NT_ACT_IDENTITY, 8>(a, grid, stream)
-                     : launch_fw_t<NT_ACT_IDENTITY, 16>(a, grid, stream);
-}
-
-#endif  // NT_DIAG
 
 // 64-row tiles: every other combination (any reduce, any aggregation act) and h > 384
 template <int CT, bool DROP = false>
@@ -275,24 +137,10 @@ int launch_fk_narrow(const fk::Args& a, int maxl, int grid, hipStream_t stream) 
 // whose act is relu / identity, or with no aggregation (fused < 0); else 64.  (The other variants
 // need more registers than two waves per SIMD hold at 128 rows.)
 int fk_tile_rows(int64_t h, int act, int reduce, int aact, bool fused) {
-  if (fk2_selected(h) || (fk_nw4_forced() && fk_nw4(h, fused, act, reduce, aact))) return 64;
+  if (fk_nw4_forced() && fk_nw4(h, fused, act, reduce, aact)) return 64;
   const bool wide_ok =
       !fused || (act == NT_ACT_RELU && reduce == NT_SUM && (aact == NT_ACT_RELU || aact == NT_ACT_IDENTITY));
   return (fk::nt_for(h) <= 24 && wide_ok) ? 128 : 64;
-}
-
-// the one-wave-per-SIMD walk for this fused layer (A/B switch fw_selected): fp32 257 <= h <= 320,
-// bf16 449 <= h <= 512 (eight column tiles per wave), relu layers with a relu / identity sum
-bool fw_active(int64_t h, int dtype, int act, int reduce, int aact) {
-#ifdef NT_DIAG
-  if (!fw_selected() || act != NT_ACT_RELU || reduce != NT_SUM || !(aact == NT_ACT_RELU || aact == NT_ACT_IDENTITY))
-    return false;
-  const int nt = fk::nt_for(h);
-  return dtype == NT_BF16 ? (h % 8 == 0 && nt > 28 && nt <= fw::kMaxNTb) : (nt > 16 && nt <= fw::kMaxNT);
-#else
-  (void)h, (void)dtype, (void)act, (void)reduce, (void)aact;
-  return false;  // the fw walk is an A/B of the diagnostic library only
-#endif
 }
 
 int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in, float* amax_out,
@@ -334,11 +182,6 @@ int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in
                NT_EUNSUPPORTED, "fp32 update: E*ld and V*ld must stay below 2^33");
     a.ldiv = a.ldic = (int)(ldi / 4);
     a.ldoc = (int)(ldo / 4);
-#ifdef NT_DIAG
-    NT_REQUIRE((ldi == u.h && ldo == u.h && u.S_part == nullptr) ||
-                   !(fk2_selected(u.h) || fw_active(u.h, NT_F32, u.act, reduce, aact)),
-               NT_EUNSUPPORTED, "diagnostic walks take dense rows and no hub partials only");
-#endif
   }
   // an even number of k-steps, at least four, per tile (update_fk_kernel runs two steps per inner
   // trip and gathers three steps ahead, within the next tile at most); a k-step past the image reads
@@ -365,30 +208,11 @@ int launch_update_fk(const UpdateArgs& u, const void* Wimg, const float* amax_in
       return e ? atoi(e) : 0;
     }();
     a.stagger = stagger;
-#ifdef NT_DIAG
-    static const int rtabl = [] {
-      const char* e = getenv("NT_FK_RTABL");
-      return e ? atoi(e) : 0;
-    }();
-    a.rtabl = rtabl;
-#endif
   }
   a.ntiles = fused ? (int)ntiles : (int)((u.E + cap - 1) / cap);
   if (a.ntiles == 0) return NT_OK;
   const int grid = a.ntiles < cu_count() ? a.ntiles : cu_count();
   const int maxl = max_in_degree - 1;  // scan rounds needed within a 16-row tile
-#ifdef NT_DIAG
-  if (fk2_selected(u.h) && !drop) {
-    a.nchunks = 1;
-    return launch_fk2(a, grid, u.stream);
-  }
-#endif
-#ifdef NT_DIAG
-  if (fused && !drop && fw_active(u.h, NT_F32, u.act, reduce, aact)) {
-    a.nchunks = 1;
-    return launch_fw(a, maxl, grid, u.stream);
-  }
-#endif
   if (fused && tile_rows <= 64 && fk_nw4(u.h, true, u.act, reduce, aact)) {
     a.nchunks = 1;
     const int g4 = a.ntiles < 2 * cu_count() ? a.ntiles : 2 * cu_count();
@@ -415,7 +239,7 @@ namespace {
 template <int ACT, int AACT, bool SUMONLY, int MAXL>
 int launch_fkb_t(const fk::Args& a, int grid, hipStream_t stream) {
   set_last_kernel("update_fk_kernel (bf16): one 8-wave workgroup per CU, 128-row tiles");
-  fk::update_fk_kernel<8, 4, ACT, AACT, SUMONLY, MAXL, 2, 0, 1><<<grid, fk::kThreads, 0, stream>>>(a);
+  fk::update_fk_kernel<8, 4, ACT, AACT, SUMONLY, MAXL, 1><<<grid, fk::kThreads, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -424,7 +248,7 @@ int launch_fkb_t(const fk::Args& a, int grid, hipStream_t stream) {
 template <int AACT, int MAXL>
 int launch_fkb4_t(const fk::Args& a, int grid, hipStream_t stream) {
   set_last_kernel("update_fk_kernel (bf16): two 4-wave workgroups per CU, 64-row tiles");
-  fk::update_fk_kernel<4, 8, NT_ACT_RELU, AACT, true, MAXL, 2, 0, 1, 4><<<grid, 256, 0, stream>>>(a);
+  fk::update_fk_kernel<4, 8, NT_ACT_RELU, AACT, true, MAXL, 1, 4><<<grid, 256, 0, stream>>>(a);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -495,19 +319,14 @@ int launch_update_fk_bf16(const UpdateArgs& u, const void* Wimg, const int32_t* 
     return launch_fkb_t<-1, NT_ACT_IDENTITY, true, 1>(a, grid, u.stream);
   }
   const int maxl = max_in_degree - 1;
-#ifdef NT_DIAG
-  if (fw_active(u.h, NT_BF16, u.act, reduce, aact)) return launch_fwb(a, maxl, grid, u.stream);
-#endif
-  {
-    if (bf16_kernel_env() == 2 && tile_rows <= 64 && relu && reduce == NT_SUM &&
-        (aact == NT_ACT_RELU || aact == NT_ACT_IDENTITY)) {
-      const int g4 = a.ntiles < 2 * cu_count() ? a.ntiles : 2 * cu_count();
-      if (aact == NT_ACT_RELU)
-        return maxl <= 3 ? launch_fkb4_t<NT_ACT_RELU, 3>(a, g4, u.stream)
-                         : launch_fkb4_t<NT_ACT_RELU, 16>(a, g4, u.stream);
-      return maxl <= 3 ? launch_fkb4_t<NT_ACT_IDENTITY, 3>(a, g4, u.stream)
-                       : launch_fkb4_t<NT_ACT_IDENTITY, 16>(a, g4, u.stream);
-    }
+  if (bf16_kernel_env() == 2 && tile_rows <= 64 && relu && reduce == NT_SUM &&
+      (aact == NT_ACT_RELU || aact == NT_ACT_IDENTITY)) {
+    const int g4 = a.ntiles < 2 * cu_count() ? a.ntiles : 2 * cu_count();
+    if (aact == NT_ACT_RELU)
+      return maxl <= 3 ? launch_fkb4_t<NT_ACT_RELU, 3>(a, g4, u.stream)
+                       : launch_fkb4_t<NT_ACT_RELU, 16>(a, g4, u.stream);
+    return maxl <= 3 ? launch_fkb4_t<NT_ACT_IDENTITY, 3>(a, g4, u.stream)
+                     : launch_fkb4_t<NT_ACT_IDENTITY, 16>(a, g4, u.stream);
   }
   if (relu && reduce == NT_SUM && aact == NT_ACT_RELU)
     return maxl <= 3   ? launch_fkb_t<NT_ACT_RELU, NT_ACT_RELU, true, 3>(a, grid, u.stream)
@@ -576,23 +395,3 @@ int amax_fill(float* ws, const float* H, int64_t nh, const float* S, int64_t ns,
 }
 
 }  // namespace nt
-
-#if defined(NT_DIAG) && FW_STAMP
-// A/B builds only (FW_STAMP): read and reset the fw kernel's stamp sums (6 values)
-extern "C" __attribute__((visibility("default"))) int nt_debug_fw_stamps(unsigned long long* out6) {
-  if (hipMemcpyFromSymbol(out6, HIP_SYMBOL(nt::g_pk_stamps), 6 * sizeof(unsigned long long), 0,
-                          hipMemcpyDeviceToHost) != hipSuccess)
-    return 2;
-  unsigned long long z[10] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(nt::g_pk_stamps), z, sizeof(z), 0, hipMemcpyHostToDevice) == hipSuccess ? 0 : 2;
-}
-#endif
-
-#ifdef NT_DIAG
-// Debug-only (diagnostic library, not part of include/notorch_amd.h): select the fp32 fused layer
-// walk (-1: the default, 0: update_fk_kernel, 1: update_fw_kernel where it applies)
-extern "C" __attribute__((visibility("default"))) int nt_debug_set_fw(int v) {
-  nt::g_fw_override = v;
-  return 0;
-}
-#endif

@@ -1,5 +1,5 @@
 // fp32 D-MPNN layer kernel on fp16 MFMA with a two-part split ("fk"), optionally fused with the
-// aggregation its output feeds.  Included by update_pk.hip.  Tiles hold at most 16 RT rows: the plan
+// aggregation its output feeds.  Included by update_fk.hip.  Tiles hold at most 16 RT rows: the plan
 // builders guarantee it and check it when they build a plan (kernels.tile_plan, host_tile_plan); the
 // kernel clamps a larger tile to its capacity (memory-safe) and keeps no device status word.
 //
@@ -109,10 +109,7 @@ struct Args {
   float* SO;  // NULL: no aggregation
   float* SP = nullptr;  // hub partial rows (slots x h fp32), written at the end rows of kFlagPart sub-runs
   int nxcd;
-  int stagger;  // diagnostic: start delay of workgroup b = stagger * ((b / nxcd) % 4) x 8k cycles (0)
-#ifdef NT_DIAG
-  int rtabl = 0;  // diagnostic library: the fw walk's timing ablations (NT_FK_RTABL, results invalid)
-#endif
+  int stagger;  // timing experiment (NT_FK_STAGGER): start delay of workgroup b = stagger * ((b / nxcd) % 4) x 8k cycles (0)
   DropMask drop;  // DROP instances (nt_dmpnn_update_fused_dropout): the mask of the update, indexed e h + j
 };
 
@@ -203,10 +200,10 @@ __device__ __forceinline__ TileHead tile_head(const Args& a, int t) {
 // The thread's row of a tile in one dependent step: the row-table entry (fused mode) or
 // {edge, src, rev} of the edge-ordered position (plain / dense mode).  Rows past the tile read the
 // tile's first row (valid memory, no branch) and are masked by row < n at use.
-template <int RT, bool TABLE>
+template <int RT, bool FROM_ROWS>
 __device__ __forceinline__ int4 row_raw(const Args& a, TileHead th, int row) {
   const int pos = th.T + (row < th.n ? row : 0);
-  if constexpr (TABLE) return a.rows[pos];
+  if constexpr (FROM_ROWS) return a.rows[pos];
   const int s = a.src ? (int)a.src[pos] : pos;
   const int q = a.rev ? (int)a.rev[pos] : -1;
   return int4{pos, s, q, kFlagStart | kFlagEnd};
@@ -227,9 +224,11 @@ __device__ __forceinline__ int4 row_entry(int4 raw, bool valid) {
 }
 
 // --------------------------------------------------------------------------- kernel
+constexpr int kGD = 2;  // gather slots: k-steps staged ahead in registers
+
 // Per-thread state of the kernel.  Plain members + force-inlined free functions taking it by
 // reference (no lambdas: closures holding pointers to these arrays kept them in scratch).
-template <int RT, int CT, int GD = 2, int PREC = 0, int NW = 8>
+template <int RT, int CT, int PREC = 0, int NW = 8>
 struct State {
   static constexpr int ROWS = 16 * RT;
   static constexpr int PPT = 2 * RT / NW;   // 16-B pieces per thread per tensor per k-step (2 or 1)
@@ -238,8 +237,8 @@ struct State {
   f32x4 acc[RT][CT];
   f32x4 bias[CT];      // bias of the thread's 4 columns per column tile, for the next epilogue
   uint4 wb[2][CT][2];  // W fragments (parity, column tile, part)
-  f32x4 gs[GD][PPT], gq[GD][PPT];  // staged pieces, GD k-steps ahead
-  int gso[GD], gqo[GD];  // their row sources
+  f32x4 gs[kGD][PPT], gq[kGD][PPT];  // staged pieces, kGD k-steps ahead
+  int gso[kGD], gqo[kGD];  // their row sources
   float mxH, mxS;
   // constants of the thread / launch
   int lane, wave, fr, g16, grt, grow, kp0, hv, hc, NT, CTC;  // hv: 16-B gather pieces per row,
@@ -252,8 +251,8 @@ struct State {
   __amdgpu_buffer_rsrc_t wrsrc;
 };
 
-template <int RT, int CT, int ACT, int P, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_gather(State<RT, CT, GD, PREC, NW>& st, const Args& a, int soff, int qoff, int s) {
+template <int RT, int CT, int ACT, int P, int PREC, int NW>
+__device__ __forceinline__ void fk_gather(State<RT, CT, PREC, NW>& st, const Args& a, int soff, int qoff, int s) {
   st.gso[P] = soff;
   st.gqo[P] = qoff;
   const int sb = soff >= 0 ? soff : 0, qb = qoff >= 0 ? qoff : 0;
@@ -262,7 +261,7 @@ __device__ __forceinline__ void fk_gather(State<RT, CT, GD, PREC, NW>& st, const
   // so the load is unconditional and the compiler's vmcnt waits stay counted
   const f32x4* H4 = reinterpret_cast<const f32x4*>(a.H ? a.H : a.S);
   // fp32: PPT pieces of 4 values; bf16: one piece of 8 values (128-row tiles), the same 8 k
-  constexpr int NP = PREC ? 1 : State<RT, CT, GD, PREC, NW>::PPT;
+  constexpr int NP = PREC ? 1 : State<RT, CT, PREC, NW>::PPT;
 #pragma unroll
   for (int u = 0; u < NP; ++u) {
     int p = PREC ? 4 * s + st.g16 : 8 * s + st.kp0 + u;
@@ -274,9 +273,9 @@ __device__ __forceinline__ void fk_gather(State<RT, CT, GD, PREC, NW>& st, const
 
 // A = S[src] - act(H[rev]) of the staged piece, scaled by s_A, split into two fp16 parts written in
 // MFMA B-fragment order (row tile grt, lane (k-group, row): 16 B per part) into LDS buffer P
-template <int RT, int CT, int ACT, int P, int BUF, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_split(State<RT, CT, GD, PREC, NW>& st, const Args& a, int s) {
-  using St = State<RT, CT, GD, PREC, NW>;
+template <int RT, int CT, int ACT, int P, int BUF, int PREC, int NW>
+__device__ __forceinline__ void fk_split(State<RT, CT, PREC, NW>& st, const Args& a, int s) {
+  using St = State<RT, CT, PREC, NW>;
   const bool sok = st.gso[P] >= 0, qok = st.gqo[P] >= 0;
   if constexpr (PREC == 1) {
     // bf16 storage: A in fp32 from the widened pieces, one rounding to bf16, one fragment part
@@ -332,8 +331,8 @@ __device__ __forceinline__ void fk_split(State<RT, CT, GD, PREC, NW>& st, const 
   }
 }
 
-template <int RT, int CT, int P, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_load_w(State<RT, CT, GD, PREC, NW>& st, int c, int s) {
+template <int RT, int CT, int P, int PREC, int NW>
+__device__ __forceinline__ void fk_load_w(State<RT, CT, PREC, NW>& st, int c, int s) {
 #pragma unroll
   for (int j = 0; j < CT; ++j) {
     // unconditional (no branch around vector-memory ops keeps the compiler's vmcnt waits counted):
@@ -379,9 +378,9 @@ __device__ __forceinline__ f32x4 fk_mac(uint4 w0r, uint4 w1r, f16x8 a0, f16x8 a1
   }
 }
 
-template <int RT, int CT, int P, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_mfma(State<RT, CT, GD, PREC, NW>& st, int c, int nrt) {
-  using St = State<RT, CT, GD, PREC, NW>;
+template <int RT, int CT, int P, int PREC, int NW>
+__device__ __forceinline__ void fk_mfma(State<RT, CT, PREC, NW>& st, int c, int nrt) {
+  using St = State<RT, CT, PREC, NW>;
   const char* bb = st.abuf + P * St::kBufB + st.lane * 16;
   // A fragments one row tile ahead; the schedule barriers keep the compiler from hoisting every row
   // tile's fragments (64 VGPRs) above the MFMAs
@@ -412,9 +411,9 @@ __device__ __forceinline__ void fk_mfma(State<RT, CT, GD, PREC, NW>& st, int c, 
 // issued by the epilogue of the previous (tile, chunk) as soon as it has stored column tile j, so
 // they land during the rest of that epilogue; fk_resid_scale multiplies them by s_A s_W before the
 // first MFMA of the K loop (48 packed multiplies per tile, no staging registers).
-template <int RT, int CT, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_resid_load(State<RT, CT, GD, PREC, NW>& st, const Args& a, int i, int c, int j) {
-  using St = State<RT, CT, GD, PREC, NW>;
+template <int RT, int CT, int PREC, int NW>
+__device__ __forceinline__ void fk_resid_load(State<RT, CT, PREC, NW>& st, const Args& a, int i, int c, int j) {
+  using St = State<RT, CT, PREC, NW>;
   int pc = 4 * (c * st.CTC + st.wave + NW * j) + st.g16;
   pc = pc < st.hc ? pc : 0;
 #pragma unroll
@@ -432,8 +431,8 @@ __device__ __forceinline__ void fk_resid_load(State<RT, CT, GD, PREC, NW>& st, c
 
 // Bias of chunk c, column tile j: an unconditional load (no bias: S's first row, zeroed at use),
 // issued a whole chunk before the epilogue that uses it.
-template <int RT, int CT, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_bias_load(State<RT, CT, GD, PREC, NW>& st, const Args& a, int c, int j) {
+template <int RT, int CT, int PREC, int NW>
+__device__ __forceinline__ void fk_bias_load(State<RT, CT, PREC, NW>& st, const Args& a, int c, int j) {
   int pc = 4 * (c * st.CTC + st.wave + NW * j) + st.g16;
   pc = (pc < st.hc && a.bias) ? pc : 0;
   if constexpr (PREC == 1) {  // raw 8 B, widened at use
@@ -444,8 +443,8 @@ __device__ __forceinline__ void fk_bias_load(State<RT, CT, GD, PREC, NW>& st, co
   }
 }
 
-template <int RT, int CT, int GD, int PREC, int NW>
-__device__ __forceinline__ void fk_resid_scale(State<RT, CT, GD, PREC, NW>& st) {
+template <int RT, int CT, int PREC, int NW>
+__device__ __forceinline__ void fk_resid_scale(State<RT, CT, PREC, NW>& st) {
   if constexpr (PREC == 1) {  // bf16: widen the raw residual pieces (no scale)
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
@@ -482,9 +481,8 @@ struct EpiCtx {
   const f32x4* H4 = nullptr;  // DROP instances: the residual rows, added behind the mask (NULL: none)
 };
 
-template <int RTI, int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC,
-          int NW>
-__device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, const Args& a, const EpiCtx& x0, int pc,
+template <int RTI, int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, bool DROP, int PREC, int NW>
+__device__ __forceinline__ void fk_epi_row(State<RT, CT, PREC, NW>& st, const Args& a, const EpiCtx& x0, int pc,
                                            bool pok, const f32x4& bj, f32x4& carry, float& ccnt) {
   if (16 * RTI < x0.n) {
     const int lo = st.lo;
@@ -515,7 +513,7 @@ __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, cons
       }
     }
     const bool rok = ri.x >= 0 && pok;
-    if (rok && (ABL & 64) == 0) {
+    if (rok) {
       if constexpr (PREC == 1) {
         reinterpret_cast<uint2*>(x0.O4)[(int64_t)ri.x * lo + pc] = ob;
       } else {
@@ -558,7 +556,7 @@ __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, cons
       }
       if ((ri.z & kFlagPart) && (ri.z & kFlagEnd) && rok) {  // a hub sub-run: its raw partial
         if constexpr (PREC == 0) reinterpret_cast<f32x4*>(a.SP)[(int64_t)ri.y * st.hc + pc] = x;
-      } else if ((ri.z & kFlagEnd) && rok && (ABL & 128) == 0) {
+      } else if ((ri.z & kFlagEnd) && rok) {
         f32x4 r = x;
         if (!SUMONLY && a.reduce == NT_MEAN) r = x / cnt;
         if constexpr (PREC == 1) {
@@ -573,11 +571,11 @@ __device__ __forceinline__ void fk_epi_row(State<RT, CT, GD, PREC, NW>& st, cons
     }
   }
   if constexpr (RTI + 1 < RT)
-    fk_epi_row<RTI + 1, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
+    fk_epi_row<RTI + 1, J, RT, CT, AACT, SUMONLY, MAXL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
 }
 
-template <int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC, int NW>
-__device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, const Args& a, const EpiCtx& x0, int i, int c,
+template <int J, int RT, int CT, int AACT, bool SUMONLY, int MAXL, bool DROP, int PREC, int NW>
+__device__ __forceinline__ void fk_epi_col(State<RT, CT, PREC, NW>& st, const Args& a, const EpiCtx& x0, int i, int c,
                                            bool load_next, int i_next, int c_next) {
   const int ct = c * st.CTC + st.wave + NW * J;
   if (ct < st.NT) {
@@ -595,7 +593,7 @@ __device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, cons
     }
     f32x4 carry = f32x4{0.f, 0.f, 0.f, 0.f};
     float ccnt = 0.f;
-    fk_epi_row<0, J, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
+    fk_epi_row<0, J, RT, CT, AACT, SUMONLY, MAXL, DROP>(st, a, x0, pc, pok, bj, carry, ccnt);
   }
   // column tile J is stored: its accumulators start the next (tile, chunk) (after the last tile the
   // loads re-read this tile's rows and go unused)
@@ -607,23 +605,23 @@ __device__ __forceinline__ void fk_epi_col(State<RT, CT, GD, PREC, NW>& st, cons
     for (int rt = 0; rt < RT; ++rt) st.acc[rt][J] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if constexpr (J + 1 < CT)
-    fk_epi_col<J + 1, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
+    fk_epi_col<J + 1, RT, CT, AACT, SUMONLY, MAXL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
 }
 
-template <int RT, int CT, int AACT, bool SUMONLY, int MAXL, int GD, int ABL, bool DROP, int PREC, int NW>
-__device__ __forceinline__ void fk_epilogue(State<RT, CT, GD, PREC, NW>& st, const Args& a, int i, int c, int n,
+template <int RT, int CT, int AACT, bool SUMONLY, int MAXL, bool DROP, int PREC, int NW>
+__device__ __forceinline__ void fk_epilogue(State<RT, CT, PREC, NW>& st, const Args& a, int i, int c, int n,
                                             bool load_next, int i_next, int c_next) {
   EpiCtx x0;
   x0.b4 = reinterpret_cast<const f32x4*>(a.bias);
   x0.O4 = reinterpret_cast<f32x4*>(a.O);
   x0.SO4 = reinterpret_cast<f32x4*>(a.SO);
-  x0.em = st.emap + (i % kEmaps) * State<RT, CT, GD, PREC, NW>::ROWS;
+  x0.em = st.emap + (i % kEmaps) * State<RT, CT, PREC, NW>::ROWS;
   x0.n = n;
   if constexpr (DROP) {
     // the accumulators hold U alone: the residual rows are fetched next to the stores (fk_epi_row)
     x0.H4 = (a.residual && a.H != nullptr) ? reinterpret_cast<const f32x4*>(a.H) : nullptr;
   }
-  fk_epi_col<0, RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
+  fk_epi_col<0, RT, CT, AACT, SUMONLY, MAXL, DROP>(st, a, x0, i, c, load_next, i_next, c_next);
 }
 
 constexpr int kLbiasB = 512 * 4;  // the bias in LDS (4-wave workgroups, h <= 512)
@@ -633,22 +631,17 @@ __device__ __forceinline__ void fk_barrier() {
   __syncthreads();
 }
 
-// ABL (diagnostic builds only, 0 in the shipping library): timing ablations, results invalid --
-// 1 gathers read row 0, 2 no MFMA, 4 no split, 8 no epilogue, 16 no per-step barrier, 32 no residual,
-// 64 no H_out stores, 128 no S_out stores; 256 (results valid): per-phase s_memtime cycle sums into
-// g_pk_stamps (0 residual scale + MFMAs, 1 W issue, 2 split + gather issue, 3 barrier, 4 epilogue,
-// 6 whole loop, 7 waves).
 // DROP: the update passes the dropout mask a.drop before the residual is added (fp32 only):
 // H_out = (residual ? H : 0) + keep U / (1 - p).  The accumulators then start at zero and hold U
 // alone, and the residual piece is loaded in the epilogue next to its store; max|H_out|, max|S_out|
 // and the aggregation are those of the values after dropout.
-template <int RT, int CT, int ACT, int AACT, bool SUMONLY, int MAXL, int GD = 2, int ABL = 0, int PREC = 0,
-          int NW = 8, bool DROP = false>
+template <int RT, int CT, int ACT, int AACT, bool SUMONLY, int MAXL, int PREC = 0, int NW = 8,
+          bool DROP = false>
 __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
   static_assert(!DROP || PREC == 0, "the dropout epilogue is fp32 only (bf16: update_bf16_kernel)");
   // fused variants (MAXL > 1) read their rows from the row table, plain ones from src / rev
-  constexpr bool TABLE = MAXL > 1;
-  using St = State<RT, CT, GD, PREC, NW>;
+  constexpr bool FROM_ROWS = MAXL > 1;
+  using St = State<RT, CT, PREC, NW>;
   constexpr int ROWS = St::ROWS;
   constexpr int kEmapB = kEmaps * ROWS * 16;
   static_assert(RT == NW || (RT == 4 && NW == 8), "row tiles per wave mapping");
@@ -725,7 +718,7 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
     st.sAW = st.sA * sW;
     st.inv = 1.f / st.sAW;  // exact: a power of two
   }
-  const bool resid = !DROP && (ABL & 32) == 0 && a.residual && a.H != nullptr;  // residual rows into the accumulators
+  const bool resid = !DROP && a.residual && a.H != nullptr;  // residual rows into the accumulators
   const bool info_writer = st.g16 == 0 && st.wave < RT;
   const int SPT = a.nchunks * a.KS;  // steps per tile
 
@@ -735,13 +728,13 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
   int4 raw2;
   TileHead h2, h3;  // h3: bounds of tile i + 3, loaded a tile before its row is
   {
-    const TileHead h0 = tile_head<RT, TABLE>(a, tile(0));
-    const int4 r0 = row_raw<RT, TABLE>(a, h0, st.grow);
-    const TileHead h1 = tile_head<RT, TABLE>(a, tile(1));
-    const int4 r1 = row_raw<RT, TABLE>(a, h1, st.grow);
-    h2 = tile_head<RT, TABLE>(a, tile(2));
-    raw2 = row_raw<RT, TABLE>(a, h2, st.grow);
-    h3 = tile_head<RT, TABLE>(a, tile(3));
+    const TileHead h0 = tile_head<RT, FROM_ROWS>(a, tile(0));
+    const int4 r0 = row_raw<RT, FROM_ROWS>(a, h0, st.grow);
+    const TileHead h1 = tile_head<RT, FROM_ROWS>(a, tile(1));
+    const int4 r1 = row_raw<RT, FROM_ROWS>(a, h1, st.grow);
+    h2 = tile_head<RT, FROM_ROWS>(a, tile(2));
+    raw2 = row_raw<RT, FROM_ROWS>(a, h2, st.grow);
+    h3 = tile_head<RT, FROM_ROWS>(a, tile(3));
     const bool v0 = st.grow < h0.n, v1 = st.grow < h1.n;
     cur = row_offsets(a, r0, v0);
     nxt = row_offsets(a, r1, v1);
@@ -792,15 +785,6 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
   // across the MFMAs.  Every vector-memory op is unconditional.
   int i = 0, c = 0;  // tile-local index, column chunk
   const int U = ntl * a.nchunks;
-  [[maybe_unused]] unsigned long long tacc[5] = {0, 0, 0, 0, 0}, tp = 0, tb = 0;
-  if constexpr ((ABL & 256) != 0) tb = tp = __builtin_amdgcn_s_memtime();
-  auto stamp = [&](int slot) __attribute__((always_inline)) {
-    if constexpr ((ABL & 256) != 0) {
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      tacc[slot] += t - tp;
-      tp = t;
-    }
-  };
   for (int u = 0; u < U; ++u) {
     // (1) residual rows (loaded by the previous epilogue) into the accumulators' scale; without a
     // residual the accumulators are zero and the scale leaves them so.  Unconditional, so that no
@@ -814,11 +798,8 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
         const int k = kb + s0 + P;
         auto phase_mfma = [&]() __attribute__((always_inline)) {
           // (2) MFMAs of step k
-          if constexpr ((ABL & 2) == 0) {
-            if (P == 0) fk_mfma<RT, CT, 0>(st, c, nrt);
-            else fk_mfma<RT, CT, 1>(st, c, nrt);
-          }
-          stamp(0);
+          if (P == 0) fk_mfma<RT, CT, 0>(st, c, nrt);
+          else fk_mfma<RT, CT, 1>(st, c, nrt);
           // (3) W fragments of step k + 2 into the registers step k used
           {
             int c2, s2;
@@ -826,39 +807,30 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
             if (P == 0) fk_load_w<RT, CT, 0>(st, c2, s2);
             else fk_load_w<RT, CT, 1>(st, c2, s2);
           }
-          stamp(1);
         };
         auto phase_split = [&]() __attribute__((always_inline)) {
           // (4) split step k + 1's staged piece into the other buffer, then gather step k + 3 into the
           // freed slot (tile i or i + 1)
           const int k1 = k + 1 < SPT ? k + 1 : k + 1 - SPT;
           const int s1 = k1 - (k1 / a.KS) * a.KS;
-          if constexpr ((ABL & 4) == 0) {
-            if (P == 0) fk_split<RT, CT, ACT, 1, 1>(st, a, s1);
-            else fk_split<RT, CT, ACT, 0, 0>(st, a, s1);
-          }
+          if (P == 0) fk_split<RT, CT, ACT, 1, 1>(st, a, s1);
+          else fk_split<RT, CT, ACT, 0, 0>(st, a, s1);
           const int k3 = k + 3;
           const int adv = k3 >= SPT ? 1 : 0;
           const int s3 = (k3 - adv * SPT) % a.KS;
-          int so = adv == 0 ? cur.x : nxt.x, qo = adv == 0 ? cur.y : nxt.y;
-          if constexpr ((ABL & 1) != 0) so = qo = 0;
+          const int so = adv == 0 ? cur.x : nxt.x, qo = adv == 0 ? cur.y : nxt.y;
           if (P == 0) fk_gather<RT, CT, ACT, 1>(st, a, so, qo, s3);
           else fk_gather<RT, CT, ACT, 0>(st, a, so, qo, s3);
-          stamp(2);
         };
         phase_mfma();
         phase_split();
-        if constexpr ((ABL & 16) == 0) fk_barrier();
-        stamp(3);
+        fk_barrier();
       }
     }
     // (5) epilogue of the unit; it starts the next (tile, chunk)'s residual loads
     const bool last_c = c + 1 == a.nchunks;
     const int i_next = last_c ? (i + 1 < ntl ? i + 1 : i) : i, c_next = last_c ? 0 : c + 1;
-    if constexpr ((ABL & 8) == 0) {
-      fk_epilogue<RT, CT, AACT, SUMONLY, MAXL, GD, ABL, DROP>(st, a, i, c, n_cur, resid, i_next, c_next);
-      stamp(4);
-    }
+    fk_epilogue<RT, CT, AACT, SUMONLY, MAXL, DROP>(st, a, i, c, n_cur, resid, i_next, c_next);
     // (6) advance: tile i + 1 becomes current, tile i + 2's row (loaded a tile ago) is published
     c = c_next;
     if (last_c) {
@@ -870,8 +842,8 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
       if (info_writer) st.emap[((i + 1) % kEmaps) * ROWS + st.grow] = row_entry(raw2, v2);
       n_nxt = h2.n < ROWS ? h2.n : ROWS;
       h2 = h3;
-      raw2 = row_raw<RT, TABLE>(a, h2, st.grow);
-      h3 = tile_head<RT, TABLE>(a, tile(i + 3));
+      raw2 = row_raw<RT, FROM_ROWS>(a, h2, st.grow);
+      h3 = tile_head<RT, FROM_ROWS>(a, tile(i + 3));
     }
   }
   if (a.amax_out) {
@@ -895,15 +867,6 @@ __global__ void __launch_bounds__(64 * NW, 2) update_fk_kernel(Args a) {
       if (a.SO) atomic_max_abs(a.amax_out + 1, bs);
     }
   }
-#ifdef NT_DIAG
-  if constexpr ((ABL & 256) != 0) {
-    if (st.lane == 0) {
-      for (int q = 0; q < 5; ++q) atomicAdd(&g_pk_stamps[q], tacc[q]);
-      atomicAdd(&g_pk_stamps[6], __builtin_amdgcn_s_memtime() - tb);
-      atomicAdd(&g_pk_stamps[7], 1ull);
-    }
-  }
-#endif
 }
 
 // Row table of a fused plan (one 16-B entry per dst-sorted position, so the layer kernel reaches a

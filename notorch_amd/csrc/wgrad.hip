@@ -11,7 +11,7 @@
 // split every fp32 value into three bf16 parts once, and store them to a double-buffered LDS slab
 // laid out [part][edge group][column] in 16-B units, so both the writes and the MFMA fragment reads
 // are contiguous 1 KiB runs (no bank conflicts).  Wave w owns a 32 x 32 quadrant: 4 MFMA tiles x 6
-// bf16 products (the bf16x6 split of csrc/update_pk.hip: fp32-accurate) per 32 edges.
+// bf16 products (a bf16x6 split: fp32-accurate) per 32 edges.
 // Partials (and the bias partials of the j-tile-0 workgroups) go to a workspace, reduced by a
 // second kernel in fixed order, so the result is deterministic.
 //
@@ -24,7 +24,7 @@
 #include "common.hpp"
 
 namespace nt {
-int cu_count();   // csrc/update_ps.hip: the current device's CU count, queried once per device
+int cu_count();   // csrc/tile_plan.hip: the current device's CU count, queried once per device
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1421,7 +1421,7 @@ WPlan make_fk_wide_plan(int64_t E, int64_t h) {
 
 }  // namespace
 
-int xcd_count();  // csrc/update_ps.hip: the current device's XCD count, queried once per device
+int xcd_count();  // csrc/tile_plan.hip: the current device's XCD count, queried once per device
 }  // namespace nt
 
 extern "C" int64_t nt_dmpnn_weight_grad_workspace(int64_t E, int64_t h) {

@@ -611,7 +611,7 @@ CHUNK_ROWS = 32  # rows per chunk of nt_segment_reduce_chunked
 
 PLAN_NCU = 256  # kernels.PLAN_NCU: the CU count the balanced plans are cut for
 PLAN_SLOTS64 = PLAN_NCU  # kernels.PLAN_SLOTS64 (64-row plans)
-WIDE_TILE_ROWS = 128  # rows of the diagnostic build's update_fk_kernel tiles (the shipping kernels: 64)
+WIDE_TILE_ROWS = 128  # rows per tile of the plan for update_fk_kernel's 128-row walk (the other walks: 64)
 
 
 def host_tile_stride(E: int, max_in_degree: int, rows: int, ncu: int) -> int:

@@ -454,7 +454,7 @@ def packed_weight_numel(h: int, dtype: torch.dtype = torch.float32) -> int:
 
 def pack_weights(W: Tensor, *, fk_only: bool = False) -> Tensor:
     """Pack one nn.Linear weight [h, h] (or a stack [L, h, h]) into the MFMA fragment image of its
-    dtype (fp32: the two-part fp16 image of the fp32 layer kernel plus the older bf16-split images;
+    dtype (fp32: the two-part fp16 image of the fp32 layer kernel, or for h % 4 != 0 the fp32 fragment image;
     bf16: one bf16 fragment image, h <= 512 or h % 8 == 0 up to 8192).  The image is an opaque
     float32-typed buffer.  fk_only (fp32): only the part nt_dmpnn_update_fused / dense_matmul read
     (nt_dmpnn_pack_weight_fk)."""
@@ -981,9 +981,11 @@ def dmpnn_row_table(perm: Tensor, dst_sorted: Tensor, src: Tensor, rev: Tensor, 
 def dense_matmul(X: Tensor, Wp: Tensor, out: Tensor | None = None, *, kernel: str = "fk",
                  amax: Tensor | None = None) -> Tensor:
     """X @ W^T for the packed image Wp of W: the layer GEMM alone.  With Wp = pack_weights(W.t()) it is
-    the backward's dA = G @ W.  fp32 (h % 4 == 0), kernel = "fk": the fp16x3 layer kernel in dense
-    mode (amax: 2 device floats whose [1] >= max|X|, else nt_absmax first; any h); "pk": the bf16x6
-    persistent kernel (h <= 304).  bf16 (h <= 512, or h % 8 == 0 up to 8192): the bf16 layer kernel
+    the backward's dA = G @ W.  fp32 (h % 4 == 0, any h <= 8192): the fp16x3 layer kernel in dense
+    mode.  kernel picks how it gets its split scale: "fk" passes amax_in (amax: 2 device floats whose
+    [1] >= max|X|, else nt_absmax first); "pk" (the name of a kernel that no longer exists) passes no
+    amax_in, so the entry point measures max|X| itself into a workspace allocated here.  bf16
+    (h <= 512, or h % 8 == 0 up to 8192): the bf16 layer kernel
     without gathers (fp32 accumulate, one rounding)."""
     dev = _require_device(X, Wp, out, amax)
     code = _require_feat("X", X)
@@ -1006,8 +1008,7 @@ def dense_matmul(X: Tensor, Wp: Tensor, out: Tensor | None = None, *, kernel: st
             _require_amax(amax, X.dtype)
     elif kernel != "pk":
         raise ValueError("kernel must be 'fk' or 'pk'")
-    # kernel = "pk" passes no amax: the diagnostic library then runs the bf16x6 kernel, the shipping one
-    # the fk kernel with max|X| written into this caller-owned workspace (ABI 6)
+    # kernel = "pk" passes no amax: the entry point writes max|X| into this caller-owned workspace (ABI 6)
     ws = torch.empty(2, dtype=torch.float32, device=dev) if amax is None else None
     _run(dev, _lib.load().nt_dmpnn_dense_matmul, _ptr(X), M, h, _ptr(Wp), NT_F32, _ptr(amax), _ptr(ws), _ptr(out),
          _stream(dev))

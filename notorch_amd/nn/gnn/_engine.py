@@ -101,7 +101,7 @@ def _note_update(kind: str, dtype: torch.dtype, h: int, rows: int = 0) -> None:
     short = launched.split(" ")[0].rstrip(":") or "update"
     if dtype == torch.bfloat16:
         info = dict(numerics="bf16 storage, bf16 MFMA, fp32 accumulate", products=1)
-    elif short in ("update_fk_kernel", "update_fw_kernel"):
+    elif short == "update_fk_kernel":
         info = dict(numerics="fp32 via scaled two-part fp16 split (3 fp16 MFMA products, fp32 accumulate)",
                     products=3)
     else:
@@ -356,10 +356,9 @@ def _entry(W: Tensor) -> list:
 
 
 def _multi_packable(W: Tensor) -> bool:
-    """fp32 weights whose image is the fk image alone (shipping library, h % 4 == 0): packed in one
-    launch pair for all layers (nt_dmpnn_pack_weights_fk), with the backward's W^T image alongside."""
-    return (W.dtype == torch.float32 and W.dim() == 2 and W.shape[0] % 4 == 0 and W.is_contiguous()
-            and not _lib.DIAG)
+    """fp32 weights whose image is the fk image alone (h % 4 == 0): packed in one launch pair for all
+    layers (nt_dmpnn_pack_weights_fk), with the backward's W^T image alongside."""
+    return W.dtype == torch.float32 and W.dim() == 2 and W.shape[0] % 4 == 0 and W.is_contiguous()
 
 
 def pack_layer_weights(weights: Sequence[Tensor], with_t: bool = False) -> list[Tensor]:
@@ -705,7 +704,7 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
         rows = min(K.fused_tile_rows(h, H.dtype, act, reduce, act),
                    K.fused_tile_rows(h, H.dtype, act, reduce, _IDENTITY))
         if rows == 128 and fp32 and h <= 320 and E <= NW4_MAX_EDGES and os.environ.get("NT_FK_NW") != "8":
-            rows = 64  # the two-workgroups-per-CU walk of 64-row tiles (update_pk.hip, fk_nw4)
+            rows = 64  # the two-workgroups-per-CU walk of 64-row tiles (update_fk.hip, fk_nw4)
         if drop is not None and not fp32:
             rows = 64  # bf16 dropout lives in the 64-row kernel's epilogue, whatever NT_BF16_KERNEL selects
     plan = fused_plan(lay, V, E, rows, H.dtype) if fusable else None

@@ -210,23 +210,10 @@ def test_block_paths_agree(fused, monkeypatch):
     assert_parity(out.node_feats, ref_node, FP32_NORM_TOL, f"node fused={fused}")
 
 
-@pytest.mark.parametrize("variant", ["pk", "ps"])
-def test_fused_kernel_variants_and_no_spin_timeouts(variant, monkeypatch):
-    """Both persistent kernels (NT_FUSED_KERNEL) agree with the oracle; the pk ring's bounded spins
-    never gave up (nt_debug_pk_timeouts)."""
-    import ctypes
-
-    from notorch_amd import _lib
-
+def test_fused_and_plain_layer_small_shapes():
+    """One relu / sum layer with a tile plan (H_out and S_out) and without one (H_out) against the
+    oracle: 7 to 300 molecules, h = 300 / 100 / 32, both rev_offset conventions of the collate."""
     K = _K()
-    if not _lib.DIAG:
-        pytest.skip("the pk / ps ring kernels are A/B variants: diagnostic library only (NT_LIB=diag)")
-    monkeypatch.setenv("NT_FUSED_KERNEL", variant)
-    lib = _lib.load()
-    fn = lib.nt_debug_pk_timeouts
-    fn.argtypes = [ctypes.POINTER(ctypes.c_uint), ctypes.c_int]
-    cnt = ctypes.c_uint(0)
-    assert fn(ctypes.byref(cnt), 1) == 0
     for h, n, rev_offset in ((300, 300, "nodes"), (300, 7, "edges"), (100, 50, "nodes"), (32, 20, "nodes")):
         G = _graph("qm9", n, seed=h + n, rev_offset=rev_offset)
         E, V = G.num_edges, G.num_nodes
@@ -241,13 +228,10 @@ def test_fused_kernel_variants_and_no_spin_timeouts(variant, monkeypatch):
         Hn, Sn = K.dmpnn_update_fused(*args, residual=True, act=relu, plan=plan, perm=perm,
                                       agg_act=relu, zero_fill=zf)
         rH, rS = _ref_layer(G, H, S, W, b, True, torch.relu, "sum", torch.relu)
-        assert_parity(Hn, rH, FP32_NORM_TOL, f"{variant} H h={h} n={n}")
-        assert_parity(Sn, rS, FP32_NORM_TOL, f"{variant} S h={h} n={n}")
+        assert_parity(Hn, rH, FP32_NORM_TOL, f"fused H h={h} n={n}")
+        assert_parity(Sn, rS, FP32_NORM_TOL, f"fused S h={h} n={n}")
         Hu, _ = K.dmpnn_update_fused(*args, residual=True, act=relu)
-        assert_parity(Hu, rH, FP32_NORM_TOL, f"{variant} unfused H h={h} n={n}")
-    torch.cuda.synchronize()
-    assert fn(ctypes.byref(cnt), 1) == 0
-    assert cnt.value == 0, "a pk ring spin gave up"
+        assert_parity(Hu, rH, FP32_NORM_TOL, f"unfused H h={h} n={n}")
 
 
 def test_host_plans_equal_device_planners():
@@ -305,7 +289,7 @@ def _n_for_tiles(pred, lo, hi, step=1):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", ["grid_eq_ntiles_mult8", "ragged_over_cus"])
 def test_xcd_walk_branches(dtype, case):
-    """Both branches of the XCD-aware tile walk (update_pk.hip / bf16.hip): (a) grid == ntiles with
+    """Both branches of the XCD-aware tile walk (update_fk.hip / bf16.hip): (a) grid == ntiles with
     ntiles % 8 == 0 (one tile per block, XCD chunks of ntiles / 8), (b) more tiles than resident
     blocks with ntiles % 8 != 0 (ragged per-XCD chunks, several tiles per block)."""
     K = _K()
@@ -338,13 +322,28 @@ def test_xcd_walk_branches(dtype, case):
 @pytest.mark.parametrize("h,M", [(300, 77_000), (300, 1), (100, 1000), (64, 4097), (4, 3)])
 def test_dense_matmul(h, M, kernel):
     """nt_dmpnn_dense_matmul (the backward's dA = G W, chemprop.py:41 under autograd): the fp16x3 fk
-    kernel's and the bf16x6 pk kernel's dense modes against fp64, fp32 contract."""
+    kernel's dense mode against fp64, fp32 contract, through both ABI branches: "fk" gives amax_in,
+    "pk" gives none, so the entry point fills the amax_ws workspace itself."""
     K = _K()
     g = torch.Generator().manual_seed(M + h)
     X, W = torch.randn(M, h, generator=g), torch.randn(h, h, generator=g) / h ** 0.5
     out = K.dense_matmul(X.to(DEV), K.pack_weights(W.t().contiguous().to(DEV)), kernel=kernel)
     ref = X.double() @ W.double()
     assert_parity(out, ref, FP32_NORM_TOL, f"dense {kernel} h={h} M={M}")
+
+
+@pytest.mark.parametrize("h,M", [(300, 77_000), (300, 1), (100, 1000), (64, 4097), (4, 3)])
+def test_dense_matmul_caller_amax(h, M):
+    """The caller-supplied bound (the engine's route): amax[1] = max|X| from K.absmax in a tensor of
+    the caller's, the shapes and the criterion of test_dense_matmul."""
+    K = _K()
+    g = torch.Generator().manual_seed(M + h)
+    X, W = torch.randn(M, h, generator=g), torch.randn(h, h, generator=g) / h ** 0.5
+    Xd = X.to(DEV)
+    amax = torch.zeros(2, dtype=torch.float32, device=DEV)
+    K.absmax(Xd, amax[1:2])
+    out = K.dense_matmul(Xd, K.pack_weights(W.t().contiguous().to(DEV)), amax=amax)
+    assert_parity(out, X.double() @ W.double(), FP32_NORM_TOL, f"dense caller amax h={h} M={M}")
 
 
 @pytest.mark.parametrize("h,M", [(640, 3000), (1024, 700)])

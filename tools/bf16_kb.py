@@ -1,5 +1,5 @@
 """Device time of the bf16 fused layer kernel (config 3 shape: zinc-4096, h = 512) for the library
-selected by NT_LIB (A/B and ablation variants, tools/r5_bf16_abl.sh).
+selected by NT_LIB (A/B variant builds: make VARIANT=<name> EXTRA=-D...).
 Usage: python tools/bf16_kb.py [--kind zinc] [--mols 4096] [--h 512] [--rounds 5]"""
 import argparse
 import os

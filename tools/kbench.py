@@ -140,7 +140,6 @@ def main():
     p.add_argument("--h", type=int, default=300)
     p.add_argument("--only", default="", help="comma list of kernels to time")
     p.add_argument("--rounds", type=int, default=5)
-    p.add_argument("--abl", default="", help="NT_LIB=diag: comma list of NT_FK_ABL ablations of fk_fused")
     a = p.parse_args()
     G = make_batch(a.kind, a.mols, seed=0).collate("nodes").to("cuda")
     if a.only == "wgrad_bf16":  # bf16 operands of its own; none of the fp32 set-up below
@@ -173,11 +172,10 @@ def main():
         rt = K.dmpnn_row_table(lay.dst_perm, plan[2], src, rev, V)
         plans[rows] = (plan, rt)
 
-    def fk(rows, abl=None):
+    def fk(rows):
         plan, rt = plans[rows]
 
         def f():
-            os.environ["NT_FK_ABL"] = str(abl or 0)
             K.dmpnn_update_fused(H, S, src, rev, Wp, b, act=relu, plan=plan, tile_rows=rows, max_in_degree=deg,
                                  perm=lay.dst_perm, agg_act=relu, amax_in=amax, amax_out=amax_out,
                                  row_table=rt, out=out, S_out=S2)
@@ -217,10 +215,8 @@ def main():
         "absmax": lambda: K.absmax(H, amax_out[0:1]),
         "pack": lambda: K.pack_weights(W),
     }
-    for n in filter(None, a.abl.split(",")):
-        fns[f"fk_abl{n}"] = fk(64, int(n))
     if a.only:
-        keep = a.only.split(",") + [k for k in fns if k.startswith("fk_abl")]
+        keep = a.only.split(",")
         fns = {k: v for k, v in fns.items() if k in keep}
     for f in fns.values():
         f()
