@@ -277,7 +277,9 @@ NT_API int nt_dmpnn_pack_weights_fk(const void* const* W, int64_t nlayers, int64
  * for h % 4 != 0 (the exact fp32 tile kernel).  (ABI 6: the library holds no device scratch.)
  * Hidden sizes: any h <= 512; above that fp32 h % 4 == 0 and bf16 h % 8 == 0 (16-byte aligned H, S,
  * H_out and b), both up to 8192; other sizes answer NT_EUNSUPPORTED, as do the same bf16 sizes in
- * nt_dmpnn_pack_weight.
+ * nt_dmpnn_pack_weight.  bf16 up to 512 with 16-byte aligned H, S, H_out and b reads and writes rows
+ * in 16-byte pieces (h % 8 == 0) or 8-byte pieces (h % 4 == 0), else element by element; the three
+ * compute the same bits.
  */
 NT_API int nt_dmpnn_update(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                     const void* Wp, const void* b, int64_t V, int64_t E, int64_t h, int residual,
@@ -371,7 +373,9 @@ NT_API int nt_dmpnn_fused_tile_rows(int64_t h, int dtype, int act, int reduce, i
  * fp32 (h % 4 == 0, any h): two-part fp16 split on fp16 MFMA (fp32 accuracy); amax_in = 2 device
  * floats >= max|H|, max|S| (from nt_dmpnn_init / the previous layer's amax_out / nt_absmax);
  * amax_out (may be NULL) = 2 zero-filled device floats raised to max|H_out|, max|S_out|.
- * bf16 (h % 8 == 0, h <= 8192; above 512 the column-pass variant): bf16 MFMA, tile_rows <= 64, amax ignored.
+ * bf16 (h % 8 == 0, h <= 8192, above 512 the column-pass variant; or h % 4 == 0, h <= 512, on 8-byte row
+ * pieces, which the training header's dropout variant answers with NT_EUNSUPPORTED): bf16 MFMA,
+ * tile_rows <= 64, amax ignored.
  * 16-byte aligned feature pointers; S_out must not alias S.
  * S_part (ABI 7, fp32, may be NULL): the hub partial rows (nt_dmpnn_hub_combine) when the row table
  * marks hub sub-runs.
@@ -514,7 +518,8 @@ NT_API int nt_gather_rows_arg(const void* base, const void* X, const int64_t* id
  * for dA = G W).  fp32 (h % 4 == 0, 16-byte aligned, out != X): the fp16x3 layer kernel without
  * gathers; amax_in = 2 device floats whose [1] >= max|X| (e.g. written by the kernel that produced
  * X), or NULL: then amax_ws (2 floats of caller-owned device memory, required) receives
- * (0, max|X|) on `stream` first.  bf16 (h <= 512, or h % 8 == 0 up to 8192): the bf16 layer kernel, amax_in / amax_ws unused. */
+ * (0, max|X|) on `stream` first.  bf16 (h <= 512, or h % 8 == 0 up to 8192): the bf16 layer kernel
+ * (row pieces as nt_dmpnn_update), amax_in / amax_ws unused. */
 NT_API int nt_dmpnn_dense_matmul(const void* X, int64_t M, int64_t h, const void* Wp, int dtype,
                                  const float* amax_in, float* amax_ws, void* out, void* stream);
 

@@ -21,6 +21,8 @@
 // HBM bytes per edge: 4 rows x 2h (read H, gather S[src], gather H[rev], write H') + 16 B indices.
 // h > 512 (h % 8 == 0, <= 8192): update_bf16_wide_kernel walks the same tile in column passes and
 // K chunks of 512 (see there).
+// h % 4 == 0, h % 8 != 0 (h <= 512): the same kernel on 8-B row pieces (W = 4: every 16-B global access
+// as two 8-B halves; the half past a row's end is never loaded into A, stored or reduced).
 #include "bf16.hpp"
 
 namespace nt {
@@ -32,12 +34,14 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;  // raw bf16 storage
 
 __device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float((unsigned)u << 16); }
 __device__ __forceinline__ bf16_t f2bf(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }
 
-// W consecutive bf16 (W = 8: one 16-B piece, 16-B aligned; W = 1: one element) <-> fp32
+// W consecutive bf16 (W = 8: one 16-B piece, 16-B aligned; W = 4: one 8-B piece, 8-B aligned; W = 1:
+// one element) <-> fp32
 template <int W>
 __device__ __forceinline__ void load_chunk(const bf16_t* __restrict__ p, float (&x)[W]) {
   if constexpr (W == 8) {
@@ -45,6 +49,14 @@ __device__ __forceinline__ void load_chunk(const bf16_t* __restrict__ p, float (
     const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      x[2 * i] = __uint_as_float(u[i] << 16);
+      x[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
+    }
+  } else if constexpr (W == 4) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    const unsigned u[2] = {v.x, v.y};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
       x[2 * i] = __uint_as_float(u[i] << 16);
       x[2 * i + 1] = __uint_as_float(u[i] & 0xffff0000u);
     }
@@ -60,6 +72,11 @@ __device__ __forceinline__ void store_chunk(bf16_t* __restrict__ p, const float 
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (__bf16)x[i];
     *reinterpret_cast<uint4*>(p) = __builtin_bit_cast(uint4, v);
+  } else if constexpr (W == 4) {
+    bf16x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (__bf16)x[i];
+    *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, v);
   } else {
     *p = f2bf(x[0]);
   }
@@ -204,19 +221,32 @@ struct BfAgg {
   bf16_t* S_out;         // V x h, rows of in-degree-0 nodes pre-zeroed by the caller
 };
 
-// S_out[node] piece = R over rows [r0, r1) of the staged values (already aact(stored H'))
-template <int R>
-__device__ __forceinline__ void reduce_rows(const float* stage, int r0, int r1, int c, float (&y)[8]) {
-  Reducer<R> red[8];
+// S_out[node] piece = R over rows [r0, r1) of the staged values (already aact(stored H')); N = 4: the
+// first half of a piece whose second half lies past the row (W == 4, h % 8 == 4)
+template <int R, int N = 8>
+__device__ __forceinline__ void reduce_rows(const float* stage, int r0, int r1, int c, float (&y)[N]) {
+  Reducer<R> red[N];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) red[q].init();
+  for (int q = 0; q < N; ++q) red[q].init();
   for (int r = r0; r < r1; ++r) {
     const float* st = stage + r * kSO + c;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) red[q].push(st[q]);
+    for (int q = 0; q < N; ++q) red[q].push(st[q]);
   }
 #pragma unroll
-  for (int q = 0; q < 8; ++q) y[q] = red[q].result();
+  for (int q = 0; q < N; ++q) y[q] = red[q].result();
+}
+
+// the same with the reduce chosen at run time
+template <int N>
+__device__ __forceinline__ void reduce_rows_by(int reduce, const float* stage, int r0, int r1, int c,
+                                               float (&y)[N]) {
+  switch (reduce) {
+    case NT_SUM: reduce_rows<NT_SUM, N>(stage, r0, r1, c, y); break;
+    case NT_MEAN: reduce_rows<NT_MEAN, N>(stage, r0, r1, c, y); break;
+    case NT_MAX: reduce_rows<NT_MAX, N>(stage, r0, r1, c, y); break;
+    default: reduce_rows<NT_MIN, N>(stage, r0, r1, c, y); break;
+  }
 }
 
 // AGG: 0 = no aggregation; 1 = fused aggregation of the stored H' (final node scatter, identity);
@@ -358,6 +388,49 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
         *reinterpret_cast<uint4*>(lds + r * lda + c * 16) = __builtin_bit_cast(uint4, a);
       }
     }
+  } else if constexpr (W == 4) {
+    // h % 4 == 0: rows are whole 8-B pieces.  The ownership of the W == 8 gather (lane c takes the
+    // c-th 8-column piece, 8 rows in flight, one 16-B LDS store per piece), each piece loaded as two
+    // 8-B halves.  The second half of a row's last piece lies past the row when h % 8 == 4: its
+    // address is clamped to the first half's (the load stays unconditional) and its four A values
+    // are the zeros of k >= h, never the loaded bits (they belong to the next row).
+    const int chunks = KS * 4;
+    constexpr int kRG = 8;
+    for (int idx = lane; idx < chunks * (16 / kRG); idx += 64) {
+      const int c = idx % chunks, r0 = 16 * w + kRG * (idx / chunks);
+      const int k0 = c * 8;
+      const bool in0 = k0 < h, in1 = k0 + 4 < h;
+      const int kc0 = in0 ? k0 : h - 4, kc1 = in1 ? k0 + 4 : kc0;
+      uint2 sraw[kRG][2], qraw[kRG][2];
+#pragma unroll
+      for (int u = 0; u < kRG; ++u) {
+        const int64_t so = soff[r0 + u], qo = qoff[r0 + u];
+        const bf16_t* sp = S + (so >= 0 ? so : 0);
+        const bf16_t* qp = H + (qo >= 0 ? qo : 0);
+        sraw[u][0] = *reinterpret_cast<const uint2*>(sp + kc0);
+        sraw[u][1] = *reinterpret_cast<const uint2*>(sp + kc1);
+        qraw[u][0] = *reinterpret_cast<const uint2*>(qp + kc0);
+        qraw[u][1] = *reinterpret_cast<const uint2*>(qp + kc1);
+      }
+#pragma unroll
+      for (int u = 0; u < kRG; ++u) {
+        const int r = r0 + u;
+        const bool sok[2] = {soff[r] >= 0 && in0, soff[r] >= 0 && in1};
+        const bool qok[2] = {qoff[r] >= 0 && in0, qoff[r] >= 0 && in1};
+        const unsigned su[4] = {sraw[u][0].x, sraw[u][0].y, sraw[u][1].x, sraw[u][1].y};
+        const unsigned qu[4] = {qraw[u][0].x, qraw[u][0].y, qraw[u][1].x, qraw[u][1].y};
+        bf16x8 a;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const unsigned sb = (i & 1) ? (su[i >> 1] & 0xffff0000u) : (su[i >> 1] << 16);
+          const unsigned qb = (i & 1) ? (qu[i >> 1] & 0xffff0000u) : (qu[i >> 1] << 16);
+          const float sv = sok[i >> 2] ? __uint_as_float(sb) : 0.f;
+          const float qv = qok[i >> 2] ? __uint_as_float(qb) : 0.f;
+          a[i] = (__bf16)(sv - act_t<ACT>(qv, act, alpha));
+        }
+        *reinterpret_cast<uint4*>(lds + r * lda + c * 16) = __builtin_bit_cast(uint4, a);
+      }
+    }
   } else {
     const int chunks = KS * 4;  // 8-element pieces per padded row
     constexpr int kRU = 4;      // rows in flight per wave
@@ -447,6 +520,21 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
 #pragma unroll
       for (int it = 0; it < kPre; ++it) hres[it] = load_res(it);
     }
+    // W == 4: the same pieces as two 8-B halves.  chi: the piece's second half is inside the row (it
+    // is not in the last piece of a row with h % 8 == 4: never loaded, stored or reduced then; its
+    // residual load is clamped to the first half's address)
+    const bool chi = cpiece + 4 < ncols;
+    uint2 hres4[kPre][2];
+    if constexpr (W == 4) {
+#pragma unroll
+      for (int it = 0; it < kPre; ++it) {
+        const int64_t e = erow[(tid >> 5) + 8 * it];
+        const bool ok = cok && e >= 0 && residual;
+        const bf16_t* hp = H + (ok ? e * h + n0 + cpiece : 0);
+        hres4[it][0] = *reinterpret_cast<const uint2*>(hp);
+        hres4[it][1] = *reinterpret_cast<const uint2*>(hp + (ok && chi ? 4 : 0));
+      }
+    }
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int j = 4 * p + jj;
@@ -498,6 +586,55 @@ __global__ void __launch_bounds__(kThreads, 2) update_bf16_kernel(
             default: reduce_rows<NT_MIN>(stage, nstart[k], nstart[k + 1], cpiece, y); break;
           }
           store_chunk<8>(agg.S_out + (int64_t)nnode[k] * h + n0 + cpiece, y);
+        }
+      }
+    } else if constexpr (W == 4) {
+      // the W == 8 epilogue with 8-B global accesses; the half past the row (!chi) is computed on
+      // whatever the staging tile holds there and dropped
+      float bb[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) bb[q] = 0.f;
+      if (bias && cok) {
+        load_chunk<4>(bias + n0 + cpiece, *reinterpret_cast<float(*)[4]>(&bb[0]));
+        if (chi) load_chunk<4>(bias + n0 + cpiece + 4, *reinterpret_cast<float(*)[4]>(&bb[4]));
+      }
+#pragma unroll
+      for (int it = 0; it < kIt; ++it) {
+        const int r = (tid >> 5) + 8 * it;
+        const int64_t e = erow[r];
+        if (cok && e >= 0) {
+          float* st = stage + r * kSO + cpiece;
+          const unsigned hu[4] = {hres4[it][0].x, hres4[it][0].y, hres4[it][1].x, hres4[it][1].y};
+          float y[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const unsigned hb = (q & 1) ? (hu[q >> 1] & 0xffff0000u) : (hu[q >> 1] << 16);
+            y[q] = st[q] + bb[q] + (residual ? __uint_as_float(hb) : 0.f);
+          }
+          bf16_t* op = out + e * h + n0 + cpiece;
+          store_chunk<4>(op, *reinterpret_cast<const float(*)[4]>(&y[0]));
+          if (chi) store_chunk<4>(op + 4, *reinterpret_cast<const float(*)[4]>(&y[4]));
+          if constexpr (AGG != 0) {  // the aggregation reads the stored (bf16) value, as unfused
+#pragma unroll
+            for (int q = 0; q < 8; ++q) st[q] = AGG == 2 ? act_t<ACT>(rbf(y[q]), act, alpha) : rbf(y[q]);
+          }
+        }
+      }
+      if constexpr (AGG != 0) {
+        __syncthreads();
+        for (int k = tid >> 5; k < nseg; k += kThreads / 32) {
+          if (!cok) continue;
+          bf16_t* sp = agg.S_out + (int64_t)nnode[k] * h + n0 + cpiece;
+          if (chi) {
+            float y[8];
+            reduce_rows_by<8>(agg.reduce, stage, nstart[k], nstart[k + 1], cpiece, y);
+            store_chunk<4>(sp, *reinterpret_cast<const float(*)[4]>(&y[0]));
+            store_chunk<4>(sp + 4, *reinterpret_cast<const float(*)[4]>(&y[4]));
+          } else {
+            float y[4];
+            reduce_rows_by<4>(agg.reduce, stage, nstart[k], nstart[k + 1], cpiece, y);
+            store_chunk<4>(sp, y);
+          }
         }
       }
     } else {
@@ -815,7 +952,8 @@ int launch_upd(const void* H, const void* S, const int64_t* src, const int64_t* 
   const int64_t slots = 2 * (int64_t)cu_count();  // two resident workgroups per CU (LDS-bound)
   const int64_t g = grid < slots ? grid : slots;
   set_last_kernel(DROP ? "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles, dropout in the epilogue"
-                       : "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles");
+                  : W == 4 ? "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles, 8-byte row pieces"
+                           : "update_bf16_kernel: two 4-wave workgroups per CU, 64-edge tiles");
   kern<<<(unsigned)g, kThreads, lds, stream>>>(
       (const bf16_t*)H, (const bf16_t*)S, src, rev, (const uint4*)Wp, (const bf16_t*)b, V, E, (int)h,
       KS, NTn, residual, act, alpha, (bf16_t*)H_out, agg, (int)grid, xcd_count(), drop);
@@ -829,11 +967,16 @@ int launch_segment_reduce_bf16(const void* X, const int32_t* seg_ptr, const int3
                                int64_t nseg, int64_t h, int reduce, int act, float alpha, void* out,
                                hipStream_t stream) {
   NT_REQUIRE(valid_reduce(reduce), NT_EINVAL, "bad reduce code");
-  const bool vec = h % 8 == 0 && aligned16(X) && aligned16(out);
-  if (vec) {
+  const int vec = row_piece(h, aligned16(X) && aligned16(out));
+  if (vec == 8) {
     const int grid = grid_for(nseg * (h / 8), 256, 256 * 32);
     NT_BF_DISPATCH_RA(reduce, act,
                       (segment_reduce_bf16<R_, A_, 8><<<grid, 256, 0, stream>>>(
+                          (const bf16_t*)X, seg_ptr, perm, nseg, h, act, alpha, (bf16_t*)out)));
+  } else if (vec == 4) {
+    const int grid = grid_for(nseg * (h / 4), 256, 256 * 32);
+    NT_BF_DISPATCH_RA(reduce, act,
+                      (segment_reduce_bf16<R_, A_, 4><<<grid, 256, 0, stream>>>(
                           (const bf16_t*)X, seg_ptr, perm, nseg, h, act, alpha, (bf16_t*)out)));
   } else {
     const int grid = grid_for(nseg * h, 256, 256 * 32);
@@ -849,16 +992,21 @@ int launch_init_bf16(const void* Xv, const void* Xe, const int64_t* src, const i
                      const int32_t* perm, int64_t V, int64_t E, int64_t h, int act, float alpha,
                      int reduce, void* H0, void* S, hipStream_t stream) {
   NT_REQUIRE(valid_reduce(reduce), NT_EINVAL, "bad reduce code");
-  const bool vec = h % 8 == 0 && aligned16(Xv) && aligned16(Xe) && aligned16(H0) &&
-                   (S == nullptr || aligned16(S));
+  const int vec = row_piece(h, aligned16(Xv) && aligned16(Xe) && aligned16(H0) && (S == nullptr || aligned16(S)));
   if (S != nullptr) {
     if (V == 0) return NT_OK;
     NT_REQUIRE(seg_ptr && (perm || E == 0), NT_EINVAL, "fused aggregation needs the dst CSR");
     NT_REQUIRE(E == 0 || (Xv && Xe && src && H0), NT_EINVAL, "NULL pointer");
-    if (vec) {
+    if (vec == 8) {
       const int grid = grid_for(V * (h / 8), 256, 256 * 32);
       NT_BF_DISPATCH_RA(reduce, act,
                         (init_aggregate_bf16<R_, A_, 8><<<grid, 256, 0, stream>>>(
+                            (const bf16_t*)Xv, (const bf16_t*)Xe, src, seg_ptr, perm, V, h, act,
+                            alpha, (bf16_t*)H0, (bf16_t*)S)));
+    } else if (vec == 4) {
+      const int grid = grid_for(V * (h / 4), 256, 256 * 32);
+      NT_BF_DISPATCH_RA(reduce, act,
+                        (init_aggregate_bf16<R_, A_, 4><<<grid, 256, 0, stream>>>(
                             (const bf16_t*)Xv, (const bf16_t*)Xe, src, seg_ptr, perm, V, h, act,
                             alpha, (bf16_t*)H0, (bf16_t*)S)));
     } else {
@@ -871,8 +1019,11 @@ int launch_init_bf16(const void* Xv, const void* Xe, const int64_t* src, const i
   } else {
     if (E == 0) return NT_OK;
     NT_REQUIRE(Xv && Xe && src && H0, NT_EINVAL, "NULL pointer");
-    if (vec)
+    if (vec == 8)
       init_only_bf16<8><<<grid_for(E * (h / 8), 256, 256 * 32), 256, 0, stream>>>(
+          (const bf16_t*)Xv, (const bf16_t*)Xe, src, E, h, (bf16_t*)H0);
+    else if (vec == 4)
+      init_only_bf16<4><<<grid_for(E * (h / 4), 256, 256 * 32), 256, 0, stream>>>(
           (const bf16_t*)Xv, (const bf16_t*)Xe, src, E, h, (bf16_t*)H0);
     else
       init_only_bf16<1><<<grid_for(E * h, 256, 256 * 32), 256, 0, stream>>>(
@@ -947,16 +1098,18 @@ int launch_update_bf16(const void* H, const void* S, const int64_t* src, const i
   NT_REQUIRE(bf16_update_supported(h), NT_EUNSUPPORTED, NT_BF16_H_RULE);
   const int64_t grid = (E + kM - 1) / kM;
   NT_REQUIRE(grid < (int64_t(1) << 31), NT_EINVAL, "too many edges");
-  const bool vec = h % 8 == 0 && aligned16(H) && aligned16(S) && aligned16(H_out) &&
-                   (b == nullptr || aligned16(b));
+  const int vec = row_piece(h, aligned16(H) && aligned16(S) && aligned16(H_out) && (b == nullptr || aligned16(b)));
   const BfAgg none{nullptr, nullptr, nullptr, 0, 0, 0.f, nullptr};
   if (h > 4 * kNWMax * 16) {
-    NT_REQUIRE(vec, NT_EINVAL, "bf16 with h > 512 needs 16-byte aligned feature pointers");
+    NT_REQUIRE(vec == 8, NT_EINVAL, "bf16 with h > 512 needs 16-byte aligned feature pointers");
     NT_BF_DISPATCH_A(act, return (launch_upd_wide<A_, 0>(H, S, src, rev, Wp, b, V, E, h, residual, act,
                                                          alpha, H_out, grid, none, stream)));
   }
-  if (vec)
+  if (vec == 8)
     NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 8, 0>(H, S, src, rev, Wp, b, V, E, h, residual,
+                                                              act, alpha, H_out, grid, none, stream)));
+  else if (vec == 4)
+    NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 4, 0>(H, S, src, rev, Wp, b, V, E, h, residual,
                                                               act, alpha, H_out, grid, none, stream)));
   else
     NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 1, 0>(H, S, src, rev, Wp, b, V, E, h, residual,
@@ -964,7 +1117,9 @@ int launch_update_bf16(const void* H, const void* S, const int64_t* src, const i
   return NT_OK;
 }
 
-bool bf16_fused_supported(int64_t h) { return h % 8 == 0 && h >= 8 && h <= 8192; }
+bool bf16_fused_supported(int64_t h) {
+  return (h % 8 == 0 && h >= 8 && h <= 8192) || (h % 4 == 0 && h >= 4 && h <= 4 * kNWMax * 16);
+}
 
 int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, const int64_t* rev,
                              const void* Wp, const void* b, int64_t V, int64_t E, int64_t h,
@@ -975,7 +1130,8 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
   NT_REQUIRE(drop == nullptr || tile_ptr != nullptr, NT_EUNSUPPORTED, "the dropout layer kernel needs a tile plan");
   if (tile_ptr == nullptr)  // no plan: the plain (unfused) kernel computes H_out only
     return launch_update_bf16(H, S, src, rev, Wp, b, V, E, h, residual, act, alpha, H_out, stream);
-  NT_REQUIRE(bf16_fused_supported(h), NT_EUNSUPPORTED, "bf16 update_fused needs h % 8 == 0, h <= 8192");
+  NT_REQUIRE(bf16_fused_supported(h) && (drop == nullptr || h % 8 == 0), NT_EUNSUPPORTED,
+             "bf16 update_fused needs " NT_BF16_FUSED_H_RULE);
   NT_REQUIRE(perm && dsts && S_out && aligned16(S_out), NT_EINVAL, "fused aggregation needs perm, "
              "dst_sorted and a 16-byte aligned S_out");
   NT_REQUIRE(ntiles > 0 && ntiles < (int64_t(1) << 31), NT_EINVAL, "bad ntiles");
@@ -1009,6 +1165,16 @@ int launch_update_bf16_fused(const void* H, const void* S, const int64_t* src, c
     else
       NT_BF_DISPATCH_A(act, return (launch_upd_wide<A_, 2>(H, S, src, rev, Wp, b, V, E, h, residual, act,
                                                            alpha, H_out, ntiles, agg, stream)));
+  }
+  if (h % 8 != 0) {  // whole 8-B pieces (h % 4 == 0, h <= 512)
+    NT_REQUIRE(aligned16(H) && aligned16(S) && aligned16(H_out) && (b == nullptr || aligned16(b)), NT_EINVAL,
+               "bf16 update_fused needs 16-byte aligned feature pointers");
+    if (aact == NT_ACT_IDENTITY)
+      NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 4, 1>(H, S, src, rev, Wp, b, V, E, h, residual,
+                                                            act, alpha, H_out, ntiles, agg, stream)));
+    else
+      NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 4, 2>(H, S, src, rev, Wp, b, V, E, h, residual,
+                                                            act, alpha, H_out, ntiles, agg, stream)));
   }
   if (aact == NT_ACT_IDENTITY)
     NT_BF_DISPATCH_A(act, return (launch_upd_nw<A_, 8, 1>(H, S, src, rev, Wp, b, V, E, h, residual,

@@ -20,24 +20,28 @@ namespace nt {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;  // raw bf16 storage
 
 __device__ __forceinline__ bf16_t f2bf(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }
 __device__ __forceinline__ float rbf(float x) { return __uint_as_float((unsigned)f2bf(x) << 16); }
 
-// W consecutive fp32 (W = 8: two 16-B loads, 16-B aligned; W = 1: one element)
+// W consecutive fp32 (W = 8: two 16-B loads, W = 4: one, 16-B aligned; W = 1: one element)
 template <int W>
 __device__ __forceinline__ void load_f32(const float* __restrict__ p, float (&x)[W]) {
   if constexpr (W == 8) {
     const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
     x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
     x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+  } else if constexpr (W == 4) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
   } else {
     x[0] = *p;
   }
 }
 
-// W consecutive bf16 from fp32 registers (W = 8: one 16-B store), each rounded once
+// W consecutive bf16 from fp32 registers (W = 8: one 16-B store, W = 4: one 8-B store), each rounded once
 template <int W>
 __device__ __forceinline__ void store_bf16(bf16_t* __restrict__ p, const float (&x)[W]) {
   if constexpr (W == 8) {
@@ -45,6 +49,11 @@ __device__ __forceinline__ void store_bf16(bf16_t* __restrict__ p, const float (
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (__bf16)x[i];
     *reinterpret_cast<uint4*>(p) = __builtin_bit_cast(uint4, v);
+  } else if constexpr (W == 4) {
+    bf16x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (__bf16)x[i];
+    *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, v);
   } else {
     *p = f2bf(x[0]);
   }
@@ -326,13 +335,18 @@ extern "C" int nt_dmpnn_init_mixed(const void* Xv, const void* Xe, const int64_t
   hipStream_t stream = as_stream(stream_);
   const float* xv = (const float*)Xv;
   const float* xe = (const float*)Xe;
-  const bool vec = h % 8 == 0 && aligned16(Xv) && aligned16(Xe) && aligned16(H0) && (S == nullptr || aligned16(S));
+  const int vec = row_piece(h, aligned16(Xv) && aligned16(Xe) && aligned16(H0) && (S == nullptr || aligned16(S)));
   if (S != nullptr) {
     if (V == 0) return NT_OK;
-    if (vec) {
+    if (vec == 8) {
       const int grid = grid_for(V * (h / 8), 256, 256 * 32);
       NT_MX_DISPATCH_RA(reduce, act,
                         (init_aggregate_mixed<R_, A_, 8><<<grid, 256, 0, stream>>>(
+                            xv, xe, src, seg_ptr, perm, V, h, act, act_alpha, (bf16_t*)H0, (bf16_t*)S)));
+    } else if (vec == 4) {
+      const int grid = grid_for(V * (h / 4), 256, 256 * 32);
+      NT_MX_DISPATCH_RA(reduce, act,
+                        (init_aggregate_mixed<R_, A_, 4><<<grid, 256, 0, stream>>>(
                             xv, xe, src, seg_ptr, perm, V, h, act, act_alpha, (bf16_t*)H0, (bf16_t*)S)));
     } else {
       const int grid = grid_for(V * h, 256, 256 * 32);
@@ -342,8 +356,11 @@ extern "C" int nt_dmpnn_init_mixed(const void* Xv, const void* Xe, const int64_t
     }
   } else {
     if (E == 0) return NT_OK;
-    if (vec)
+    if (vec == 8)
       init_only_mixed<8><<<grid_for(E * (h / 8), 256, 256 * 32), 256, 0, stream>>>(xv, xe, src, E, h,
+                                                                                  (bf16_t*)H0);
+    else if (vec == 4)
+      init_only_mixed<4><<<grid_for(E * (h / 4), 256, 256 * 32), 256, 0, stream>>>(xv, xe, src, E, h,
                                                                                   (bf16_t*)H0);
     else
       init_only_mixed<1><<<grid_for(E * h, 256, 256 * 32), 256, 0, stream>>>(xv, xe, src, E, h, (bf16_t*)H0);

@@ -457,8 +457,11 @@ static int update_fused(const void* H, const void* S, const int64_t* src, const 
   NT_REQUIRE(reduce >= NT_SUM && reduce <= NT_MIN, NT_EINVAL, "bad reduce code");
   NT_REQUIRE(V >= 0 && E >= 0 && E < (int64_t(1) << 31) && V < (int64_t(1) << 31) && h > 0, NT_EINVAL,
              "bad sizes");
-  NT_REQUIRE(dtype == NT_BF16 ? bf16_fused_supported(h) : (h % 4 == 0 && h <= 8192), NT_EUNSUPPORTED,
-             "update_fused needs h % 4 == 0 (fp32) or h % 8 == 0 (bf16), h <= 8192");
+  // bf16: rows of whole 16-B pieces, or of whole 8-B pieces up to 512 (no dropout instances of those)
+  NT_REQUIRE(dtype == NT_BF16 ? bf16_fused_supported(h) && (drop == nullptr || h % 8 == 0)
+                              : (h % 4 == 0 && h <= 8192),
+             NT_EUNSUPPORTED,
+             "update_fused needs h % 4 == 0, h <= 8192 (fp32), or bf16 " NT_BF16_FUSED_H_RULE);
   if (E == 0) return NT_OK;
   NT_REQUIRE(H && S && src && rev && Wp && H_out, NT_EINVAL, "NULL pointer");
   if (drop) {

@@ -575,8 +575,9 @@ def dmpnn_init_mixed(
 ) -> tuple[Tensor, Tensor | None]:
     """dmpnn_init from fp32 Xv / Xe to bf16 outputs (nt_dmpnn_init_mixed): H0 = bf16(Xv[src] + Xe), added
     in fp32 and rounded once, optionally fused with S = scatter(act(H0), dst) (needs the dst CSR;
-    the bits of segment_reduce over that H0).  Rows of whole 16-byte pieces (h % 8 == 0, which the
-    allocator's alignment then guarantees) move as vectors, other rows by element."""
+    the bits of segment_reduce over that H0).  Rows of whole 16-byte pieces (h % 8 == 0) or 8-byte pieces
+    (h % 4 == 0) of 16-byte aligned tensors (the allocator's alignment) move as vectors, other rows by
+    element."""
     dev = _require_device(Xv, Xe, src, seg_ptr, perm)
     _require_f32("node_feats", Xv)
     _require_f32("edge_feats", Xe)
@@ -690,9 +691,10 @@ def dmpnn_update(
 
 def fused_supported(V: int, E: int, h: int, dtype: torch.dtype = torch.float32) -> bool:
     """Shapes nt_dmpnn_update_fused accepts: the fp32 fk kernel (h % 4 == 0, h <= 8192) or the bf16
-    tile kernel (h % 8 == 0, h <= 8192; above 512 its column-pass variant)."""
+    tile kernel (h % 8 == 0, h <= 8192, above 512 its column-pass variant; or h % 4 == 0, h <= 512, on
+    8-byte row pieces, which nt_dmpnn_update_fused_dropout does not take)."""
     if dtype == torch.bfloat16:
-        return h % 8 == 0 and 8 <= h <= 8192 and E < 2**31
+        return ((h % 8 == 0 and 8 <= h <= 8192) or (h % 4 == 0 and 4 <= h <= 512)) and E < 2**31
     return (dtype == torch.float32 and h % 4 == 0 and 4 <= h <= 8192 and E * h // 4 < 2**31
             and V * h // 4 < 2**31 and E < 2**31 and V < 2**31)
 

@@ -14,8 +14,8 @@ Forward (per call, all on ``torch.cuda.current_stream()``, inputs already reside
 d + 1 launches (+ one nt_dmpnn_pack_weights_fk launch pair per new set of weights).  Training-mode
 dropout keeps that sequence: nt_dmpnn_update_fused_dropout applies layer l's mask (p, seed,
 dropout_offset(l, E, h)) to the update in the layer kernel's epilogue, ahead of the residual add and
-the aggregation (NT_FUSED_DROPOUT=0, or bf16 above BF16_FUSED_DROPOUT_MAX_H: the unfused sequence
-below).  Otherwise (no fused plan):
+the aggregation (NT_FUSED_DROPOUT=0, or bf16 above BF16_FUSED_DROPOUT_MAX_H or with h % 8 != 0: the unfused
+sequence below).  Otherwise (no fused plan):
 
     nt_dmpnn_init; for l: nt_dmpnn_update, nt_segment_reduce; nt_segment_reduce (node)   2 + 2d launches
       (dropout: nt_dmpnn_update without its residual, then nt_dropout_residual adds it back)
@@ -85,6 +85,20 @@ FP32_WGRAD_FK_MAX_H = 4096
 # h = 512; above it the column-pass kernel's dropout epilogue is tested at kernel level
 # but not timed, so those blocks keep the unfused update + nt_dropout_residual + segment reduce.
 BF16_FUSED_DROPOUT_MAX_H = 512
+# bf16 rows of whole 8-byte pieces (h % 8 == 4, h <= 512) in the fused layer launch
+# (update_bf16_kernel<.., W = 4, ..>): with False those blocks keep the plain update + segment reduce per
+# layer, while nt_dmpnn_update_fused still takes these sizes at the launch level.  Measured at h = 300 on
+# config 2's batch against the parent commit's library (three alternating fresh-process runs):
+# forward 0.256-0.257 ms against 1.020-1.021 (bf16 storage) and 0.274-0.277 against 1.046-1.055 (bf16
+# autocast), the parent's spread 0.001 / 0.009 ms; the training step 1.74-1.76 against 2.63-2.64 ms.
+BF16_FUSED_PIECE4 = True
+
+
+def _bf16_backward_kernels(V: int, E: int, h: int) -> bool:
+    """bf16 shapes whose backward runs dA on the layer kernel's dense mode (the W^T images packed in the
+    forward) and dW on the weight-gradient kernel: rows of whole 16-byte pieces.  Narrower than
+    K.fused_supported: h % 8 == 4 keeps the library dA / dW (moving it changes gradient bits)."""
+    return h % 8 == 0 and 8 <= h <= 8192 and E < 2**31
 
 # Optional per-launch timer for the dominant kernel (bench.py sets it): a list that receives
 # (start, end) torch.cuda.Event pairs recorded on the launch stream around every nt_dmpnn_update.
@@ -674,7 +688,7 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
     """The d layers + final node scatter, from H0 and layer 0's aggregation S.  drop = (p, seed):
     training-mode dropout of every layer's update.  On a graph with a fused plan the layer kernel
     applies the mask in its epilogue (nt_dmpnn_update_fused_dropout, one launch per layer, the fp32
-    amax chain kept); without a plan, in bf16 above BF16_FUSED_DROPOUT_MAX_H, or with NT_FUSED_DROPOUT=0,
+    amax chain kept); without a plan, in bf16 above BF16_FUSED_DROPOUT_MAX_H or with h % 8 != 0, or with NT_FUSED_DROPOUT=0,
     the update runs without its residual and nt_dropout_residual adds it back.  amax (fp32): the split scales, row 0 filled by the init
     (see _amax_buffer)."""
     d = len(weights)
@@ -689,7 +703,7 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
         # bf16 compute on fp32 master parameters (bf16 autocast): their bf16 images and bias copies, and
         # in a training forward whose backward runs dA on the bf16 layer kernel the W^T images, in one launch
         Wps, biases = pack_layer_weights_bf16(
-            weights, biases, with_t=keep_states and K.fused_supported(V, E, h, torch.bfloat16))
+            weights, biases, with_t=keep_states and _bf16_backward_kernels(V, E, h))
     else:
         Wps = pack_layer_weights(weights, with_t=keep_states and H.dtype == torch.float32)
     fp32 = H.dtype == torch.float32
@@ -697,8 +711,11 @@ def _layers_forward(H, S, V, src, rev, lay, weights, biases, act, reduce, residu
         amax = _amax_buffer(d, H)
         K.absmax(H, amax[0, 0:1])
         K.absmax(S, amax[0, 1:2])
-    drop_fusable = drop is None or (_fused_dropout_enabled() and (fp32 or h <= BF16_FUSED_DROPOUT_MAX_H))
-    fusable = drop_fusable and _fused_enabled() and K.fused_supported(V, E, h, H.dtype)
+    # bf16 rows of 8-byte pieces (h % 8 == 4): no dropout instances, and the launch behind BF16_FUSED_PIECE4
+    drop_fusable = drop is None or (_fused_dropout_enabled()
+                                    and (fp32 or (h % 8 == 0 and h <= BF16_FUSED_DROPOUT_MAX_H)))
+    fusable = (drop_fusable and _fused_enabled() and K.fused_supported(V, E, h, H.dtype)
+               and (fp32 or h % 8 == 0 or BF16_FUSED_PIECE4))
     rows = 64
     if fusable:  # the layer kernel's tile capacity for every layer of this block
         rows = min(K.fused_tile_rows(h, H.dtype, act, reduce, act),
@@ -1100,10 +1117,10 @@ def block_backward(dnode, dH, states, weights, src, dst, rev, lay, act, reduce, 
         Gu = Gu.contiguous()
         fk_dense = fp32 and K.fused_supported(V, E, h, Gu.dtype)
         fk_wgrad = fp32 and wgrad == "kernel" and (h <= 320 or (h % 4 == 0 and h <= FP32_WGRAD_FK_MAX_H))
-        # bf16: dA runs on the layer kernel's dense mode at every h it supports, dW on the
+        # bf16: dA runs on the layer kernel's dense mode at every h of _bf16_backward_kernels, dW on the
         # weight-gradient kernel (above h = 512 its variant that tiles dW in both dimensions) up to
         # BF16_WGRAD_MAX_H, on the library GEMM above
-        bf16_da = Gu.dtype == torch.bfloat16 and wgrad != "library" and K.fused_supported(V, E, h, Gu.dtype)
+        bf16_da = Gu.dtype == torch.bfloat16 and wgrad != "library" and _bf16_backward_kernels(V, E, h)
         bf16_wgrad = bf16_da and h <= BF16_WGRAD_MAX_H
         gmax = gmax_cur if drop is None else None  # dropout rescales G: its max is taken afresh
         if (fk_dense or fk_wgrad) and gmax is None:  # max|G|: the split scale of both fp16-split kernels
