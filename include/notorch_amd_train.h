@@ -121,6 +121,29 @@ NT_API int nt_dmpnn_update_fused_dropout(const void* H, const void* S, const int
                                          int64_t ld_in, int64_t ld_out, float p, uint64_t seed, uint64_t offset,
                                          void* stream);
 
+/*
+ * The attention readouts (Gated, SDPAttention) under torch.autocast(dtype=bfloat16): bf16 node rows X
+ * with fp32 keys (Gated's a / a_bias, SDPAttention's Q).  Every key element is rounded to bf16, to
+ * nearest even, where the kernel loads it; from there the arithmetic is that of the NT_BF16 kernels of
+ * nt_node_scores / nt_softmax_pool_backward, so the results are the bits those entry points return for
+ * the bf16 copy of the key, and no bf16 copy of a key is written.  nt_softmax_pool reads no key and
+ * serves both.  dtype is the dtype of X (and of out / dout / dX): NT_BF16, else NT_EUNSUPPORTED.
+ * Arguments, shapes and validation order: those of nt_node_scores / nt_softmax_pool_backward, on the
+ * host before any device call (NT_EINVAL for bad sizes, for both or neither of a and Q, and for a NULL
+ * pointer).  Rows of whole 16-byte pieces (h % 8 == 0, 16-byte aligned X and key; the backward also
+ * out, dout and dX) move as vectors, a key piece as two 16-byte loads per lane; others by element.
+ * One wave per node row.  ds and P are fp32 and are not rounded: the caller forms the fp32 key
+ * gradients from them (Gated da = sum_g P[g], db = sum_v ds[v]; SDPA dQ = P / sqrt_key).
+ */
+NT_API int nt_node_scores_mixed(const void* X, int64_t n, int64_t h, const void* a, const void* a_bias,
+                                const void* Q, const int64_t* node_seg, float sqrt_key, int dtype,
+                                float* scores, void* stream);
+NT_API int nt_softmax_pool_backward_mixed(const void* X, const float* scores, const int32_t* seg_ptr,
+                                          const int32_t* perm, const int64_t* node_seg, int64_t nseg,
+                                          int64_t n, int64_t h, const void* out, const void* dout,
+                                          const void* a, const void* Q, float sqrt_key, int dtype,
+                                          float* stats, void* dX, float* ds, float* P, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,12 @@ EXT_SIGNATURES: dict[str, tuple] = {
          _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_f32, _c_int, _vp, _vp, _vp, _vp, _vp, _c_i64,
          _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _vp],
     ),
+    # nt_node_scores / nt_softmax_pool_backward for bf16 X and fp32 keys (the attention readouts under autocast)
+    "nt_node_scores_mixed": (
+        _c_int, [_vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_f32, _c_int, _vp, _vp],
+    ),
+    "nt_softmax_pool_backward_mixed": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp,
+                                                _vp, _c_f32, _c_int, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

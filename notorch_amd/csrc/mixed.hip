@@ -10,11 +10,18 @@
 //   nt_dmpnn_init_embed_mixed    the same from fp32 embedding tables and the type indices (bags summed
 //                                in fp32 in ascending j): nt_embed_bag (fp32) twice + nt_dmpnn_init_mixed,
 //                                bit for bit, with Xv / Xe never written
+//   nt_node_scores_mixed         the readout scores of bf16 rows against an fp32 key (Gated's a / a_bias,
+//                                SDPAttention's Q), the key rounded as it is loaded: nt_node_scores (bf16)
+//                                on the bf16 copy of the key, bit for bit
+//   nt_softmax_pool_backward_mixed  the same for nt_softmax_pool_backward: its per-node kernel with the fp32
+//                                key; the per-molecule statistics and P are readout.hip's own launches
 //
 // Every rounding is round-to-nearest-even (v_cvt_pk_bf16_f32), the rounding of torch's .to(bfloat16).
 // All kernels of this file are new; no kernel of another translation unit changes.
 #include "../../include/notorch_amd_train.h"
 #include "bf16.hpp"
+#include "readout.hpp"
+#include "rows.hpp"
 
 namespace nt {
 namespace {
@@ -261,7 +268,129 @@ __global__ void __launch_bounds__(256) init_embed_only_mixed(EmbedMixedArgs a,
   }
 }
 
-#define NT_MX_DISPATCH_A(ACT, LAUNCH)                                            \
+// ------------------------------------------------------------------------------ attention readouts
+// node_scores_kernel and pool_node_backward_kernel of readout.hip at T = bf16 with the key (Gated's a
+// and a_bias, SDPAttention's Q) read from fp32: N key elements (N = 8: two 16-B loads per lane) rounded
+// to bf16 as they are loaded.  Everything after the load is those kernels' code (same lane -> column
+// map, same fmaf chain, same butterfly), so the bits are theirs on the bf16 copy of the key.
+template <bool VEC>
+struct KeyPiece {
+  static constexpr int N = VEC ? 8 : 1;
+  __device__ __forceinline__ static void load(const float* __restrict__ p, float (&y)[N]) {
+    load_f32<N>(p, y);
+#pragma unroll
+    for (int i = 0; i < N; ++i) y[i] = rbf(y[i]);
+  }
+};
+
+template <bool VEC, bool SDPA>
+__global__ void __launch_bounds__(256) node_scores_mixed_kernel(
+    const bf16_raw* __restrict__ X, const int64_t* __restrict__ node_seg, int64_t n, int64_t h,
+    const float* __restrict__ a, const float* __restrict__ a_bias, const float* __restrict__ Q,
+    float sqrt_key, float* __restrict__ s) {
+  constexpr int N = Piece<bf16_raw, VEC>::N;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t v = wave; v < n; v += nwaves) {
+    const float* q = a;
+    if constexpr (SDPA) q = Q + node_seg[v] * h;
+    float part = 0.f;
+    for (int64_t c = (int64_t)lane * N; c < h; c += 64 * N) {
+      float x[N], y[N];
+      Piece<bf16_raw, VEC>::load(X + v * h + c, x);
+      KeyPiece<VEC>::load(q + c, y);
+#pragma unroll
+      for (int i = 0; i < N; ++i) part = fmaf(x[i], y[i], part);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    if (lane == 0) {
+      float sc = part;
+      if constexpr (SDPA) {
+        sc = sc / sqrt_key;
+      } else if (a_bias) {
+        sc += rbf(*a_bias);
+      }
+      s[v] = sc;
+    }
+  }
+}
+
+template <bool VEC, bool SDPA>
+__global__ void __launch_bounds__(256) pool_node_backward_mixed_kernel(
+    const bf16_raw* __restrict__ X, const float* __restrict__ s, const int64_t* __restrict__ node_seg,
+    const float* __restrict__ stats, const bf16_raw* __restrict__ dout, int64_t n, int64_t h,
+    const float* __restrict__ a, const float* __restrict__ Q, float sqrt_key, bf16_raw* __restrict__ dX,
+    float* __restrict__ ds) {
+  constexpr int N = Piece<bf16_raw, VEC>::N;
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  for (int64_t v = wave; v < n; v += nwaves) {
+    const int64_t g = node_seg[v];
+    const float alpha = expf(s[v] - stats[3 * g]) / stats[3 * g + 1];
+    float part = 0.f;
+    for (int64_t c = (int64_t)lane * N; c < h; c += 64 * N) {
+      float x[N], y[N];
+      Piece<bf16_raw, VEC>::load(X + v * h + c, x);
+      Piece<bf16_raw, VEC>::load(dout + g * h + c, y);
+#pragma unroll
+      for (int i = 0; i < N; ++i) part = fmaf(x[i], y[i], part);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    const float dsv = alpha * (part - stats[3 * g + 2]);
+    for (int64_t c = (int64_t)lane * N; c < h; c += 64 * N) {
+      float k[N], y[N], o[N];
+      Piece<bf16_raw, VEC>::load(dout + g * h + c, y);
+      if constexpr (SDPA) {
+        KeyPiece<VEC>::load(Q + g * h + c, k);
+#pragma unroll
+        for (int i = 0; i < N; ++i) k[i] /= sqrt_key;
+      } else {
+        KeyPiece<VEC>::load(a + c, k);
+      }
+#pragma unroll
+      for (int i = 0; i < N; ++i) o[i] = fmaf(alpha, y[i], dsv * k[i]);
+      Piece<bf16_raw, VEC>::store(dX + v * h + c, o);
+    }
+    if (lane == 0) ds[v] = dsv;
+  }
+}
+
+template <bool VEC>
+int launch_scores_mixed(const void* X, const int64_t* node_seg, int64_t n, int64_t h, const void* a,
+                        const void* a_bias, const void* Q, float sqrt_key, float* s, hipStream_t stream) {
+  const int grid = grid_for(n * 64, 256, 256 * 32);
+  if (Q)
+    node_scores_mixed_kernel<VEC, true><<<grid, 256, 0, stream>>>(
+        (const bf16_raw*)X, node_seg, n, h, nullptr, nullptr, (const float*)Q, sqrt_key, s);
+  else
+    node_scores_mixed_kernel<VEC, false><<<grid, 256, 0, stream>>>(
+        (const bf16_raw*)X, nullptr, n, h, (const float*)a, (const float*)a_bias, nullptr, 1.f, s);
+  NT_LAUNCH_CHECK();
+  return NT_OK;
+}
+
+template <bool VEC>
+int launch_node_backward_mixed(const void* X, const float* s, const int64_t* node_seg, const float* stats,
+                               const void* dout, int64_t n, int64_t h, const void* a, const void* Q,
+                               float sqrt_key, void* dX, float* ds, hipStream_t stream) {
+  const int grid = grid_for(n * 64, 256, 256 * 32);
+  if (Q)
+    pool_node_backward_mixed_kernel<VEC, true><<<grid, 256, 0, stream>>>(
+        (const bf16_raw*)X, s, node_seg, stats, (const bf16_raw*)dout, n, h, nullptr, (const float*)Q, sqrt_key,
+        (bf16_raw*)dX, ds);
+  else
+    pool_node_backward_mixed_kernel<VEC, false><<<grid, 256, 0, stream>>>(
+        (const bf16_raw*)X, s, node_seg, stats, (const bf16_raw*)dout, n, h, (const float*)a, nullptr, 1.f,
+        (bf16_raw*)dX, ds);
+  NT_LAUNCH_CHECK();
+  return NT_OK;
+}
+
+#define NT_MX_DISPATCH_A(ACT, LAUNCH)                                          \
   do {                                                                           \
     if ((ACT) == NT_ACT_IDENTITY) { constexpr int A_ = NT_ACT_IDENTITY; LAUNCH; } \
     else if ((ACT) == NT_ACT_RELU) { constexpr int A_ = NT_ACT_RELU; LAUNCH; }    \
@@ -415,4 +544,50 @@ extern "C" int nt_dmpnn_init_embed_mixed(const void* node_table, int64_t num_nod
   }
   NT_LAUNCH_CHECK();
   return NT_OK;
+}
+
+extern "C" int nt_node_scores_mixed(const void* X, int64_t n, int64_t h, const void* a, const void* a_bias,
+                                    const void* Q, const int64_t* node_seg, float sqrt_key, int dtype,
+                                    float* scores, void* stream_) {
+  using namespace nt;
+  clear_error();
+  NT_REQUIRE(dtype == NT_BF16, NT_EUNSUPPORTED, "dtype (of X) must be NT_BF16; the keys are fp32");
+  NT_REQUIRE(n >= 0 && h > 0, NT_EINVAL, "bad sizes");
+  NT_REQUIRE((a == nullptr) != (Q == nullptr), NT_EINVAL, "exactly one of a (Gated) and Q (SDPA)");
+  NT_REQUIRE(Q == nullptr || (node_seg && sqrt_key > 0.f), NT_EINVAL, "SDPA needs node_seg, sqrt_key > 0");
+  if (n == 0) return NT_OK;
+  NT_REQUIRE(X && scores, NT_EINVAL, "NULL pointer");
+  hipStream_t stream = as_stream(stream_);
+  const bool vec = h % 8 == 0 && aligned16(X) && aligned16(a ? a : Q);
+  return vec ? launch_scores_mixed<true>(X, node_seg, n, h, a, a_bias, Q, sqrt_key, scores, stream)
+             : launch_scores_mixed<false>(X, node_seg, n, h, a, a_bias, Q, sqrt_key, scores, stream);
+}
+
+extern "C" int nt_softmax_pool_backward_mixed(const void* X, const float* scores, const int32_t* seg_ptr,
+                                              const int32_t* perm, const int64_t* node_seg, int64_t nseg,
+                                              int64_t n, int64_t h, const void* out, const void* dout,
+                                              const void* a, const void* Q, float sqrt_key, int dtype,
+                                              float* stats, void* dX, float* ds, float* P, void* stream_) {
+  using namespace nt;
+  clear_error();
+  NT_REQUIRE(dtype == NT_BF16, NT_EUNSUPPORTED, "dtype (of X, out, dout, dX) must be NT_BF16; the key is fp32");
+  NT_REQUIRE(nseg >= 0 && n >= 0 && h > 0, NT_EINVAL, "bad sizes");
+  NT_REQUIRE((a == nullptr) != (Q == nullptr), NT_EINVAL, "exactly one of a (Gated) and Q (SDPA)");
+  NT_REQUIRE(Q == nullptr || sqrt_key > 0.f, NT_EINVAL, "SDPA needs sqrt_key > 0");
+  if (nseg == 0) return NT_OK;
+  NT_REQUIRE(X && scores && seg_ptr && node_seg && out && dout && stats && dX && ds && P, NT_EINVAL,
+             "NULL pointer");
+  hipStream_t stream = as_stream(stream_);
+  const bool vec = h % 8 == 0 && aligned16(X) && aligned16(out) && aligned16(dout) && aligned16(dX) &&
+                   aligned16(a ? a : Q);
+  // the three launches of nt_softmax_pool_backward; only the per-node kernel reads the key
+  int rc = launch_pool_stats_bf16(vec, scores, seg_ptr, perm, out, dout, nseg, h, stats, stream);
+  if (rc != NT_OK) return rc;
+  if (n > 0) {
+    rc = vec ? launch_node_backward_mixed<true>(X, scores, node_seg, stats, dout, n, h, a, Q, sqrt_key, dX, ds, stream)
+             : launch_node_backward_mixed<false>(X, scores, node_seg, stats, dout, n, h, a, Q, sqrt_key, dX, ds,
+                                                 stream);
+    if (rc != NT_OK) return rc;
+  }
+  return launch_weighted_pool_bf16(vec, X, ds, seg_ptr, perm, nseg, h, P, stream);
 }

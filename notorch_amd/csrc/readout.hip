@@ -314,3 +314,47 @@ extern "C" int nt_softmax_pool_backward(const void* X, const float* scores, cons
              : launch_pool_backward<bf16_raw, false>(X, scores, seg_ptr, perm, node_seg, nseg, n, h, out, dout, a,
                                                      Q, sqrt_key, stats, dX, ds, P, stream);
 }
+
+// readout.hpp: the key-free launches of launch_pool_backward<bf16_raw, VEC>, for mixed.hip.  Templates below
+// the entry points, so that every kernel is still instantiated from launch_pool_backward first and the
+// translation unit emits its kernels in the order it always did.
+#include "readout.hpp"
+
+namespace nt {
+namespace {
+
+template <bool VEC>
+int launch_stats_bf16(const float* s, const int32_t* seg_ptr, const int32_t* perm, const void* out,
+                      const void* dout, int64_t nseg, int64_t h, float* stats, hipStream_t stream) {
+  pool_stats_kernel<bf16_raw, VEC><<<grid_for(nseg * 64, 256, 256 * 32), 256, 0, stream>>>(
+      s, seg_ptr, perm, (const bf16_raw*)out, (const bf16_raw*)dout, nseg, h, stats);
+  NT_LAUNCH_CHECK();
+  return NT_OK;
+}
+
+template <bool VEC>
+int launch_wpool_bf16(const void* X, const float* ds, const int32_t* seg_ptr, const int32_t* perm,
+                      int64_t nseg, int64_t h, float* P, hipStream_t stream) {
+  constexpr int N = Piece<bf16_raw, VEC>::N;
+  weighted_pool_kernel<bf16_raw, VEC><<<grid_for(nseg * (h / N), 256, 256 * 32), 256, 0, stream>>>(
+      (const bf16_raw*)X, ds, seg_ptr, perm, nseg, h, P);
+  NT_LAUNCH_CHECK();
+  return NT_OK;
+}
+
+}  // namespace
+
+int launch_pool_stats_bf16(bool vec, const float* s, const int32_t* seg_ptr, const int32_t* perm,
+                           const void* out, const void* dout, int64_t nseg, int64_t h, float* stats,
+                           hipStream_t stream) {
+  return vec ? launch_stats_bf16<true>(s, seg_ptr, perm, out, dout, nseg, h, stats, stream)
+             : launch_stats_bf16<false>(s, seg_ptr, perm, out, dout, nseg, h, stats, stream);
+}
+
+int launch_weighted_pool_bf16(bool vec, const void* X, const float* ds, const int32_t* seg_ptr,
+                              const int32_t* perm, int64_t nseg, int64_t h, float* P, hipStream_t stream) {
+  return vec ? launch_wpool_bf16<true>(X, ds, seg_ptr, perm, nseg, h, P, stream)
+             : launch_wpool_bf16<false>(X, ds, seg_ptr, perm, nseg, h, P, stream);
+}
+
+}  // namespace nt

@@ -49,6 +49,8 @@ __all__ = [
     "pack_weights_mixed",
     "dmpnn_init_mixed",
     "dmpnn_init_embed_mixed",
+    "node_scores_mixed",
+    "softmax_pool_backward_mixed",
 ]
 
 
@@ -1443,6 +1445,98 @@ def softmax_pool_backward(X: Tensor, scores: Tensor, seg_ptr: Tensor, perm: Tens
     _run(dev, _lib.load().nt_softmax_pool_backward,
          _ptr(X), _ptr(scores), _ptr(seg_ptr), _ptr(perm), _ptr(node_seg), nseg, n, h, _ptr(out), _ptr(dout),
          _ptr(a), _ptr(Q), float(sqrt_key), code, _ptr(stats), _ptr(dX), _ptr(ds), _ptr(P), _stream(dev))
+    return dX, ds, P
+
+
+def _require_f32_key(name: str, t: Tensor) -> None:
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 on the mixed readout path, got {t.dtype} "
+                        "(operands of one dtype take node_scores / softmax_pool_backward)")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _require_mixed_readout(X: Tensor, a: Tensor | None, a_bias: Tensor | None, Q: Tensor | None,
+                           node_seg: Tensor | None) -> None:
+    """bf16 X (n x h, contiguous) with exactly one fp32 key: a (h entries, with an optional fp32 a_bias of
+    one entry) or Q (b x h, with batch_node_index)."""
+    if X.dtype != torch.bfloat16:
+        raise TypeError(f"X must be bfloat16 on the mixed readout path, got {X.dtype}")
+    if X.dim() != 2:
+        raise ValueError("X must be n x h")
+    if not X.is_contiguous():
+        raise ValueError("X must be contiguous")
+    h = X.shape[1]
+    if (a is None) == (Q is None):
+        raise ValueError("pass exactly one of a (Gated) and Q (SDPAttention)")
+    if a is not None:
+        _require_f32_key("a", a)
+        if a.numel() != h:
+            raise ValueError("a must have h entries")
+        if a_bias is not None:
+            _require_f32_key("a_bias", a_bias)
+            if a_bias.numel() != 1:
+                raise ValueError("a_bias must have one entry")
+    else:
+        _require_f32_key("Q", Q)
+        if Q.dim() != 2 or Q.shape[1] != h:
+            raise RuntimeError(f"Q must be b x {h}, got {tuple(Q.shape)}")
+        if a_bias is not None:
+            raise ValueError("a_bias goes with a (Gated)")
+        if node_seg is None:
+            raise ValueError("SDPAttention scores need batch_node_index")
+    if node_seg is not None:
+        _require_i64("batch_node_index", node_seg)
+        if node_seg.numel() != X.shape[0]:
+            raise ValueError("batch_node_index must have one entry per row of X")
+
+
+def node_scores_mixed(X: Tensor, *, a: Tensor | None = None, a_bias: Tensor | None = None,
+                      Q: Tensor | None = None, node_seg: Tensor | None = None,
+                      sqrt_key: float = 1.0) -> Tensor:
+    """node_scores for bf16 X and fp32 keys (nt_node_scores_mixed): every element of a / a_bias / Q is
+    rounded to bf16 (to nearest even) where the kernel loads it, so the scores are the bits of
+    node_scores on a.to(bfloat16) / Q.to(bfloat16) with no bf16 copy of the key written.  A bf16 key
+    belongs to node_scores."""
+    _require_mixed_readout(X, a, a_bias, Q, node_seg)
+    dev = _require_device(X, a, a_bias, Q, node_seg)
+    n, h = X.shape
+    s = torch.empty(n, dtype=torch.float32, device=dev)
+    _run(dev, _lib.load().nt_node_scores_mixed,
+         _ptr(X), n, h, _ptr(a), _ptr(a_bias), _ptr(Q), _ptr(node_seg), float(sqrt_key), NT_BF16,
+         _ptr(s), _stream(dev))
+    return s
+
+
+def softmax_pool_backward_mixed(X: Tensor, scores: Tensor, seg_ptr: Tensor, perm: Tensor | None,
+                                node_seg: Tensor, nseg: int, out: Tensor, dout: Tensor, *,
+                                a: Tensor | None = None, Q: Tensor | None = None,
+                                sqrt_key: float = 1.0) -> tuple[Tensor, Tensor, Tensor]:
+    """softmax_pool_backward for bf16 X / out / dout and an fp32 key (nt_softmax_pool_backward_mixed): the
+    key is rounded to bf16 where the kernel loads it; (dX bf16, ds fp32, P fp32) are the bits of
+    softmax_pool_backward on the rounded key.  The fp32 key's gradient is formed from ds and P by the
+    caller and stays fp32."""
+    _require_mixed_readout(X, a, None, Q, node_seg)
+    for name, t in (("out", out), ("dout", dout)):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{name} must be bfloat16 on the mixed readout path, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.dim() != 2 or t.shape[0] != nseg or t.shape[1] != X.shape[1]:
+            raise ValueError(f"{name} must be nseg x h")
+    if scores.dtype != torch.float32 or scores.numel() != X.shape[0] or not scores.is_contiguous():
+        raise ValueError("scores must be contiguous fp32 with one entry per row of X")
+    if seg_ptr.dtype != torch.int32 or seg_ptr.numel() != nseg + 1:
+        raise ValueError("seg_ptr must be int32 of length nseg + 1")
+    dev = _require_device(X, scores, seg_ptr, perm, node_seg, out, dout, a, Q)
+    n, h = X.shape
+    dX = torch.empty_like(X)
+    ds = torch.empty(n, dtype=torch.float32, device=dev)
+    P = torch.empty(nseg, h, dtype=torch.float32, device=dev)
+    stats = torch.empty(max(3 * nseg, 1), dtype=torch.float32, device=dev)
+    _run(dev, _lib.load().nt_softmax_pool_backward_mixed,
+         _ptr(X), _ptr(scores), _ptr(seg_ptr), _ptr(perm), _ptr(node_seg), nseg, n, h, _ptr(out), _ptr(dout),
+         _ptr(a), _ptr(Q), float(sqrt_key), NT_BF16, _ptr(stats), _ptr(dX), _ptr(ds), _ptr(P), _stream(dev))
     return dX, ds, P
 
 

@@ -12,6 +12,14 @@ uses alpha as the (V, 1) node weight agg.py:59-61 evidently means: the reference
 and returns (b, V, d) — O(b V d) memory and not a readout.  This is the one documented divergence.
 Training through them runs the kernel backward (``nt_softmax_pool_backward``): the gradients of X,
 of Gated's ``a`` and of SDPAttention's query Q.
+
+Mixed precision: inside ``torch.autocast("cuda", dtype=torch.bfloat16)`` the two attention readouts take
+bf16 ``node_feats`` (what a block returns there) together with fp32 keys (``Gated.a.weight`` / ``a.bias``,
+SDPAttention's ``Q``).  ``nt_node_scores_mixed`` / ``nt_softmax_pool_backward_mixed`` round each key element
+to bf16 where they load it, so the output and dX are the bits of the bf16-storage readout on the rounded
+keys and no torch cast of a parameter runs; an fp32 key receives its fp32 gradient unrounded.  Outside a
+bf16 autocast region (fp16 autocast and a nested ``autocast(enabled=False)`` included) the pair raises the
+``TypeError`` of operands of two dtypes; operands of one dtype run as they do outside autocast.
 """
 from __future__ import annotations
 
@@ -89,31 +97,34 @@ class SoftmaxPoolFunction(torch.autograd.Function):
     key: Gated's a.weight (1 x d) with bias (1,) or None; SDPAttention's Q (b x d) with bias None."""
 
     @staticmethod
-    def forward(ctx, X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B):
+    def forward(ctx, X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B, mixed=False):
+        node_scores = K.node_scores_mixed if mixed else K.node_scores
         if sdpa:
-            scores = K.node_scores(X, Q=key.contiguous(), node_seg=bni.contiguous(), sqrt_key=sqrt_key)
+            scores = node_scores(X, Q=key.contiguous(), node_seg=bni.contiguous(), sqrt_key=sqrt_key)
         else:
-            scores = K.node_scores(X, a=key.detach().reshape(-1).contiguous(),
-                                   a_bias=None if bias is None else bias.detach())
+            scores = node_scores(X, a=key.detach().reshape(-1).contiguous(),
+                                 a_bias=None if bias is None else bias.detach())
         out = K.softmax_pool(X, scores, mol_ptr, mol_perm, B)
         ctx.save_for_backward(X, key, scores, out, bni)
-        ctx.cfg = (sdpa, sqrt_key, mol_ptr, mol_perm, B, bias is not None)
+        ctx.cfg = (sdpa, sqrt_key, mol_ptr, mol_perm, B, bias is not None, mixed)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         X, key, scores, out, bni = ctx.saved_tensors
-        sdpa, sqrt_key, mol_ptr, mol_perm, B, has_bias = ctx.cfg
+        sdpa, sqrt_key, mol_ptr, mol_perm, B, has_bias, mixed = ctx.cfg
         k = key.detach().contiguous() if sdpa else key.detach().reshape(-1).contiguous()
-        dX, ds, P = K.softmax_pool_backward(
+        pool_backward = K.softmax_pool_backward_mixed if mixed else K.softmax_pool_backward
+        dX, ds, P = pool_backward(
             X, scores, mol_ptr, mol_perm, bni.contiguous(), B, out, dout.contiguous().to(X.dtype),
             a=None if sdpa else k, Q=k if sdpa else None, sqrt_key=sqrt_key)
+        # ds and P are fp32: an fp32 key (mixed) keeps them unrounded, a bf16 key rounds them once here
         if sdpa:
             dkey, dbias = (P / sqrt_key).to(key.dtype), None
         else:
             dkey = P.sum(0).reshape(key.shape).to(key.dtype)
             dbias = ds.sum().reshape(1).to(key.dtype) if has_bias else None
-        return dX, dkey, dbias, None, None, None, None, None, None
+        return dX, dkey, dbias, None, None, None, None, None, None, None
 
 
 class _AttentionReadout(Aggregation):
@@ -129,14 +140,20 @@ class _AttentionReadout(Aggregation):
         B = len(G)
         mol_ptr, mol_perm = _engine.mol_layout(G)
         bni = G.batch_node_index
-        if sdpa and (key.dim() != 2 or key.shape[1] != X.shape[1]):
-            raise RuntimeError(f"Q must be b x {X.shape[1]}, got {tuple(key.shape)}")
+        if sdpa and (key.dim() != 2 or key.shape[1] != X.shape[1] or key.shape[0] < B):
+            raise RuntimeError(f"Q must be b x {X.shape[1]} with b >= {B}, got {tuple(key.shape)}")
+        # bf16 rows with fp32 keys inside a bf16 autocast region (a bf16 block's node_feats, the module's
+        # fp32 parameters): the mixed kernels round the keys as they load them.  Anywhere else the pair is
+        # rejected by the plain bindings (TypeError), as every other pair of unequal dtypes is.
+        mixed = (X.dtype == torch.bfloat16 and key.dtype == torch.float32
+                 and (bias is None or bias.dtype == torch.float32) and _engine.autocast_bf16(X.device))
         needs_grad = torch.is_grad_enabled() and (
             X.requires_grad or key.requires_grad or (bias is not None and bias.requires_grad))
         if needs_grad:
-            return SoftmaxPoolFunction.apply(X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B)
+            return SoftmaxPoolFunction.apply(X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B, mixed)
         with torch.no_grad():
-            return SoftmaxPoolFunction.forward(_NoCtx(), X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B)
+            return SoftmaxPoolFunction.forward(_NoCtx(), X, key, bias, sdpa, sqrt_key, mol_ptr, mol_perm, bni, B,
+                                               mixed)
 
 
 class _NoCtx:

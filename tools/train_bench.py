@@ -21,11 +21,15 @@ forward under no_grad: it drops too).  By default the layer kernel applies the m
 nt_dropout_residual and a separate segment reduce.  With --dropout the JSON also carries the layer
 launch the forward took and its median time (the engine's event pair around every layer launch: on
 the unfused path it spans the update and the dropout kernel, not the segment reduce that follows).
+--readout gated trains a Gated attention readout (its fp32 a.weight / a.bias in the optimizer) in place of
+Sum; with --autocast it runs inside the region on the block's bf16 node_feats (nt_node_scores_mixed,
+nt_softmax_pool_backward_mixed).  --readout gated-f32 is the A/B for that: node_feats widened to fp32 by
+torch and the readout on the fp32 kernels outside the region, what mixed precision had to run before.
 The table and the JSON also report torch.cuda.max_memory_allocated over the timed steps.
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
                                   [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--autocast]
-                                  [--dropout P] [--json]"""
+                                  [--dropout P] [--readout sum|gated|gated-f32] [--json]"""
 import argparse
 import contextlib
 import json
@@ -38,7 +42,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from notorch_amd.data.synth import make_batch  # noqa: E402
-from notorch_amd.nn import ChempropBlock, EmbeddedChempropBlock, GraphEmbedding, Sum  # noqa: E402
+from notorch_amd.nn import ChempropBlock, EmbeddedChempropBlock, Gated, GraphEmbedding, Sum  # noqa: E402
 
 
 def main():
@@ -70,6 +74,10 @@ def main():
     p.add_argument("--dropout", type=float, default=0.0,
                    help="dropout probability of every layer's update (training mode; NT_FUSED_DROPOUT=0 keeps "
                         "it off the fused layer launch)")
+    p.add_argument("--readout", default="sum", choices=["sum", "gated", "gated-f32"],
+                   help="sum: the Sum readout; gated: a trained Gated readout on the block's output as it is "
+                        "(under --autocast: bf16 rows, fp32 keys, inside the region); gated-f32: the same readout "
+                        "on node_feats.float(), outside the autocast region")
     p.add_argument("--json", action="store_true", help="print one JSON object instead of the table")
     a = p.parse_args()
     if a.autocast and a.dtype != "f32":
@@ -83,7 +91,7 @@ def main():
     dt = {"f32": torch.float32, "bf16": torch.bfloat16}[a.dtype]
     G = make_batch(a.kind, a.mols, seed=a.seed).collate("nodes")
     torch.manual_seed(0)
-    ro = Sum()
+    ro = Sum() if a.readout == "sum" else Gated(a.h).to("cuda", dt).train()
     E = G.num_edges
     if a.embedded:
         os.environ["NT_EMBED_BWD"] = a.embed_bwd
@@ -101,24 +109,32 @@ def main():
         Xe_d = Gd.edge_feats.requires_grad_(True)
     opt = None
     if a.optim != "none":
-        opt = torch.optim.Adam(blk.parameters(), lr=1e-4, **({"fused": True} if a.optim == "adam-fused" else {}))
+        opt = torch.optim.Adam([*blk.parameters(), *ro.parameters()], lr=1e-4,
+                               **({"fused": True} if a.optim == "adam-fused" else {}))
+
+    def read(out):
+        if a.readout != "gated-f32":
+            return ro(out)
+        with torch.autocast("cuda", enabled=False):
+            return ro(out.update(node_feats=out.node_feats.float()))
 
     def step():
         blk.zero_grad(set_to_none=True)
+        ro.zero_grad(set_to_none=True)
         with region():
             if a.embedded:
                 out = blk(Gd)
             else:
                 Xv_d.grad = Xe_d.grad = None
                 out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
-            loss = ro(out).float().pow(2).sum()
+            loss = read(out).float().pow(2).sum()
         loss.backward()
         if opt is not None:
             opt.step()
 
     def fwd():
         with torch.no_grad(), region():
-            ro(blk(Gd))
+            read(blk(Gd))
 
     res = {}
     mem = {}
@@ -166,6 +182,7 @@ def main():
             "weight_grad": os.environ.get("NT_WGRAD", "default"), "optim": a.optim,
             **({"embedded": True, "embed_bwd": a.embed_bwd} if a.embedded else {}),
             **({"autocast": "bf16"} if a.autocast else {}),
+            **({"readout": a.readout} if a.readout != "sum" else {}),
             **layer,
             "max_memory_allocated": mem,
             "warmup": a.warmup, "steps": a.steps,
@@ -174,6 +191,7 @@ def main():
         return
     print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}"
           + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else "") + (" autocast=bf16" if a.autocast else "")
+          + (f" readout={a.readout}" if a.readout != "sum" else "")
           + (f" dropout={a.dropout} layer {layer['layer_us']:.1f} us: {layer['layer_kernel']}" if layer else ""))
     for k, v in res.items():
         print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s  "
