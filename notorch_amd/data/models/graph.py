@@ -60,17 +60,22 @@ class DeviceLayout:
     batch_node_index: Optional[Tensor] = None
     validated: bool = False  # src/dst in [0,V), rev in [0,E) checked
     # fused-update tile plan (tile_ptr, ntiles, dst_sorted, zero_fill), derived lazily on the device
-    # by notorch_amd.nn.gnn._engine.fused_plan; False = not available (in-degree > 32)
+    # by notorch_amd.nn.gnn._layout.fused_plan; False = not available (in-degree > 32)
     plan: object = None
     # the fp32 layer kernel's wider plan: (tile_ptr, ntiles) of node-aligned tiles of <= 128 rows,
     # balanced over PLAN_NCU CUs (dst_sorted / zero_fill as in `plan`); False = not available
     plan_wide: object = None
-    # backward CSRs (src -> nodes, rev_index -> edges), built lazily by _engine.backward_layout
-    bwd: object = None
-    # the fp32 layer kernel's row table (key, rev_index, E x 4 int32), built lazily by _engine.row_table
-    row_table: object = None
-    # the fused embedding init's type records (key, E x 4 int32), built lazily by _engine.embed_records
-    embed_records: object = None
+    # Device-side entries built lazily by notorch_amd.nn.gnn._layout, each stored by its _cached as
+    # (pinned object, value, *key).  map_tensors carries none of them, so a moved layout rebuilds them.
+    bwd: object = None  # backward CSRs (src_ptr, src_perm, rev_ptr, rev_perm): backward_layout
+    row_table: object = None  # the fp32 layer kernel's row table, E x 4 int32: row_table
+    embed_records: object = None  # the fused embedding init's type records, E x 4 int32: embed_records
+    zero_rows: object = None  # which node-row outputs need a zero fill (out, mid, bwd): zero_rows_needed
+    hub_runs: object = None  # the row table with hub sub-runs (table, nslots, hubs, slot_ptr): hub_run_table
+    hub_chunk_ids: object = None  # the dst chunk plan's chunks inside hub segments, int32: hub_chunk_ids
+    da_plan: object = None  # the backward's src-sorted dA + dS tile plan and row table, or None: dA_plan
+    # (weakref node types, weakref edge types, (versions, table sizes)) the embedded block last validated
+    embed_checked: object = None
     # host-computed statistics the collate ships with the CSR, so a fresh batch needs no
     # device -> host sync: (max, min) in-degree, largest molecule, (min, max) type index of the
     # node / edge feature columns when they are integer type matrices

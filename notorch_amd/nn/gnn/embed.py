@@ -154,7 +154,9 @@ class EmbeddedChempropBlock(nn.Module):
         # the layout needs V: give dst_layout a graph whose node_feats has V rows (the type matrix)
         lay = _engine.dst_layout(G)
         node_types, edge_types = G.node_feats.contiguous(), G.edge_feats.contiguous()
-        seen = getattr(lay, "embed_checked", None)
+        # not through _layout._cached: the entry holds the type tensors weakly (a pinned object would keep
+        # a batch's features alive with its layout) and is written only after a forward that passed
+        seen = lay.embed_checked
         # the check is against these table sizes: a smaller table must re-validate the indices
         key = (node_types._version, edge_types._version, emb.node.num_embeddings, emb.edge.num_embeddings)
         validate = not (
@@ -173,7 +175,7 @@ class EmbeddedChempropBlock(nn.Module):
                 *[l.linear.weight for l in layers], *[l.linear.bias for l in layers],
             )
         else:
-            node, H = _engine.block_forward_embedded(
+            node, H, _ = _engine.block_forward_embedded(
                 emb.node.weight.detach(), node_types, emb.edge.weight.detach(), edge_types,
                 G.edge_index[0].contiguous(), G.rev_index.contiguous(), lay,
                 [l.linear.weight for l in layers], [l.linear.bias for l in layers], act, blk.reduce,

@@ -164,9 +164,9 @@ def test_rrelu_training_backward_replays_forward_draws():
     Xe_t = Gd.edge_feats.clone().requires_grad_()
     layers = blk._chemprop_layers()
     torch.cuda.manual_seed(11)
-    _, H = _engine._torch_block_layerwise(Gd.node_feats, Xe_t, Gd.edge_index, Gd.rev_index,
-                                          [l.linear.weight for l in layers], [l.linear.bias for l in layers],
-                                          [l.act for l in layers], "sum", True, [None, None])
+    _, H = _engine._torch_block(Gd.node_feats, Xe_t, Gd.edge_index, Gd.rev_index,
+                                [l.linear.weight for l in layers], [l.linear.bias for l in layers],
+                                [l.act for l in layers], "sum", True, [None, None])
     assert_parity(out.edge_feats.detach(), H.detach(), FP32_NORM_TOL, "H (same draws)")
     H.sum().backward()
     assert_parity(Xe_d.grad, Xe_t.grad, FP32_NORM_TOL, "dXe")
