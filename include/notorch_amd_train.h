@@ -144,6 +144,28 @@ NT_API int nt_softmax_pool_backward_mixed(const void* X, const float* scores, co
                                           const void* a, const void* Q, float sqrt_key, int dtype,
                                           float* stats, void* dX, float* ds, float* P, void* stream);
 
+/*
+ * The ranking part of the Rank-N-Contrast loss (notorch/nn/loss/rnc.py:39-79) for sim and dist, both
+ * n x n fp32, contiguous: with s_ik = exp(sim[i,k] / temp) and
+ *   denom_ij = eps + sum_{k : dist[i,k] >= dist[i,j]} s_ik             (k over all of 0..n-1: k = j always,
+ *                                                                       k = i when dist[i,j] <= dist[i,i])
+ *   row_nll[i] = sum_{j != i} ( log denom_ij - sim[i,j] / temp )       (n floats; loss = sum / (n (n - 1)))
+ *   dsim[i,k]  = ( s_ik * T_ik - [k != i] ) / (temp * n * (n - 1)),    T_ik = sum_{j != i, dist[i,j] <= dist[i,k]}
+ *                                                                              1 / denom_ij
+ * dsim (n x n, the gradient of the mean loss with respect to sim, diagonal included) may be NULL: the
+ * forward only.  dist takes part in comparisons only (as floats: -0 == +0) and gets no gradient.
+ * One workgroup per row sorts it by dist descending (a fixed bitonic network in LDS) and scans it;
+ * O(n^2) memory, no n x n x n mask.  Every sum runs in a fixed order: two calls on the same inputs return
+ * the same bits.  Non-finite entries are not checked (the result is then unspecified; the call ends).
+ * nt_rnc_max_n() is the largest n a workgroup's LDS and thread count hold (>= 4096).
+ * Checked on the host before any device call: NULL sim / dist / row_nll, n < 0, temp not finite or
+ * <= 0 (NT_EINVAL); n > nt_rnc_max_n() (NT_EUNSUPPORTED); n == 0 launches nothing.  Rows move as
+ * 16-byte vectors when n % 4 == 0 and the pointers are 16-byte aligned, else by element.
+ */
+NT_API int nt_rnc_max_n(void);
+NT_API int nt_rnc_rank(const float* sim, const float* dist, int64_t n, float temp, float eps, float* row_nll,
+                       float* dsim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,9 @@ EXT_SIGNATURES: dict[str, tuple] = {
     ),
     "nt_softmax_pool_backward_mixed": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp,
                                                 _vp, _c_f32, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    # the ranking part of RankNContrastLoss (csrc/rnc.hip): sim, dist, n, temp, eps, row_nll, dsim | NULL
+    "nt_rnc_max_n": (_c_int, []),
+    "nt_rnc_rank": (_c_int, [_vp, _vp, _c_i64, _c_f32, _c_f32, _vp, _vp, _vp]),
 }
 
 

@@ -51,6 +51,8 @@ __all__ = [
     "dmpnn_init_embed_mixed",
     "node_scores_mixed",
     "softmax_pool_backward_mixed",
+    "rnc_max_n",
+    "rnc_rank",
 ]
 
 
@@ -1566,3 +1568,24 @@ def dropout_residual(Y: Tensor, p: float, seed: int, offset: int = 0, *, base: T
     return out
 
 
+# ------------------------------------------------------------------------- Rank-N-Contrast loss
+def rnc_max_n() -> int:
+    """Largest n of rnc_rank (what one workgroup's LDS and threads hold; the library's constant)."""
+    return int(_lib.load().nt_rnc_max_n())
+
+
+def rnc_rank(sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool) -> tuple[Tensor, Tensor | None]:
+    """The ranking part of RankNContrastLoss for n x n fp32 sim and dist (nt_rnc_rank): row_nll[i] =
+    sum_{j != i} (log denom_ij - sim_ij / temp) and, with need_grad, dsim = d(mean loss) / d sim from
+    the same launch (else None: no n x n buffer is allocated)."""
+    dev = _require_device(sim, dist)
+    _require_f32("sim", sim)
+    _require_f32("dist", dist)
+    if sim.dim() != 2 or sim.shape[0] != sim.shape[1] or dist.shape != sim.shape:
+        raise ValueError(f"sim and dist must be n x n, got {tuple(sim.shape)} and {tuple(dist.shape)}")
+    n = sim.shape[0]
+    row_nll = torch.empty(n, dtype=torch.float32, device=dev)
+    dsim = torch.empty_like(sim) if need_grad else None
+    _run(dev, _lib.load().nt_rnc_rank,
+         _ptr(sim), _ptr(dist), n, float(temp), float(eps), _ptr(row_nll), _ptr(dsim), _stream(dev))
+    return row_nll, dsim
