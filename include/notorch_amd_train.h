@@ -166,6 +166,71 @@ NT_API int nt_rnc_max_n(void);
 NT_API int nt_rnc_rank(const float* sim, const float* dist, int64_t n, float temp, float eps, float* row_nll,
                        float* dsim, void* stream);
 
+/*
+ * The task losses and regression metrics of notorch/nn/loss/loss.py and notorch/nn/metrics.py: element
+ * loss, masked weighted reduction and the gradient of the reduced loss (csrc/task_loss.hip).
+ *
+ * preds: b x t x c, contiguous, preds_dtype NT_F32 or NT_BF16 (widened as loaded); targets: b x t fp32.
+ * mask, lt_mask, gt_mask: b x t bytes (0 = false), each may be NULL; sample_weights: b fp32 or NULL.
+ * kind selects the element loss L[i,j] of preds[i,j,:] = p and targets[i,j] = y:
+ *   NT_LOSS_MSE  (c = 1)  (p - y)^2
+ *   NT_LOSS_MAE  (c = 1)  |p - y|
+ *   NT_LOSS_RMSE (c = 1)  sqrt((p - y)^2): the reference's literal definition, equal to MAE
+ *   NT_LOSS_BCE  (c = 1)  max(p, 0) - p y + log1p(exp(-|p|))        (binary_cross_entropy_with_logits)
+ *   NT_LOSS_MVE  (c = 2)  p = (m, v): (m - y)^2 / (2 v) + log(2 pi v) / 2
+ *   NT_LOSS_EVIDENTIAL (c = 4)  p = (m, v, alpha, beta), r = y - m, B = 2 beta (1 + v):
+ *                         log(pi / v) / 2 - alpha log B + (alpha + 1/2) log(v r^2 + B) + lgamma(alpha)
+ *                         - lgamma(alpha + 1/2) + v_kl ((2 v + alpha) |r| - eps)
+ *   NT_LOSS_XENT (c >= 1) logsumexp(p) - p[(int)y]; a class index outside [0, c) makes the element NaN
+ * With lt_mask / gt_mask (MSE, MAE, RMSE only) p is first replaced by y where (p < y and lt) or (p > y and
+ * gt); such an element has zero loss and zero gradient.  v_kl and eps are read by NT_LOSS_EVIDENTIAL only.
+ *   loss[0]       = sum_ij L[i,j] w[i] m[i,j] / den,   den = sum_ij m[i,j]  (mask) or b t (mask == NULL)
+ *   dpreds[i,j,:] = dL[i,j]/dp * (w[i] m[i,j] / den)                       (preds_dtype; NULL: loss only)
+ * w = 1 without sample_weights.  An all-false mask gives NaN (0 / 0), as in the reference.  MAE and RMSE
+ * take the gradient sign(p - y), 0 at p == y.  Evidential's digamma is the recurrence up to x >= 6 followed
+ * by the asymptotic series (NaN for alpha <= 0).  Non-finite inputs are not checked.
+ *
+ * b t <= nt_task_loss_single_max(): ONE launch of one workgroup, no workspace.  Above it: one workgroup per
+ * nt_task_loss_single_max() elements writes a partial sum and a partial mask count, one workgroup adds them
+ * in index order and leaves 1 / den in the workspace, and (with dpreds) a third launch writes the gradient.
+ * Every sum runs in an order fixed by (b, t): per-thread partials in index order (fp64), a fixed shuffle
+ * tree, the waves in order; no float atomics; two calls return the same bits.  Nothing is read back.
+ * workspace: nt_task_loss_workspace(b, t) bytes (0 in the one-launch case: NULL is accepted then) of
+ * caller-owned device memory, 16-byte aligned.
+ * Checked on the host before any device call: NULL preds / targets / loss, b, t < 0 or c < 1 or sizes beyond
+ * 2^40 elements, a c that does not fit the kind, bounds with another kind than MSE / MAE / RMSE, a short or
+ * missing workspace (NT_EINVAL); an unknown kind or preds_dtype (NT_EUNSUPPORTED).  b t == 0 launches
+ * nothing (loss is not written).
+ */
+enum { NT_LOSS_MSE = 0, NT_LOSS_MAE = 1, NT_LOSS_RMSE = 2, NT_LOSS_BCE = 3, NT_LOSS_MVE = 4,
+       NT_LOSS_EVIDENTIAL = 5, NT_LOSS_XENT = 6 };
+NT_API int64_t nt_task_loss_single_max(void);
+/* bytes of workspace for these sizes; -1 for bad sizes */
+NT_API int64_t nt_task_loss_workspace(int64_t b, int64_t t);
+NT_API int nt_task_loss(const void* preds, int preds_dtype, const float* targets, const uint8_t* mask,
+                        const float* sample_weights, const uint8_t* lt_mask, const uint8_t* gt_mask, int64_t b,
+                        int64_t t, int64_t c, int kind, float v_kl, float eps, float* loss, void* dpreds,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * AUROC and average precision of the columns of scores and targets (both n x t fp32, contiguous), one
+ * workgroup per column (csrc/rank_metric.hip).  The label of an entry is ignored where mask (n x t bytes,
+ * may be NULL) is 0, else positive where (int)target == 1, negative where (int)target == 0, ignored otherwise.
+ * The column is sorted by score descending (the bitonic network of nt_rnc_rank; -0 == +0; ignored entries
+ * are padding behind everything), the prefix counts tp and fp of positives and negatives are integers, and
+ * both metrics are evaluated at the end g of each group of equal scores:
+ *   AUROC = sum_g (fp_g - fp_{g-1}) (tp_g + tp_{g-1}) / (2 P N)      (the trapezoid over distinct thresholds
+ *           = Mann-Whitney with ties counted half; the sum is exact in 64-bit integers, divided once)
+ *   AP    = sum_g ((tp_g - tp_{g-1}) / P) tp_g / (tp_g + fp_g)       (fp64, in a fixed order)
+ * out: t x 4 fp32: AUROC, AP, P, N of each column; AUROC and AP are NaN when P == 0 or N == 0.
+ * Two calls return the same bits.  Checked on the host before any device call: NULL scores / targets / out,
+ * n < 0 or t < 0 or t >= 2^31 (NT_EINVAL); n > nt_rank_metric_max_n() (>= 4096; NT_EUNSUPPORTED).  t == 0
+ * launches nothing; n == 0 writes NaN, NaN, 0, 0.
+ */
+NT_API int nt_rank_metric_max_n(void);
+NT_API int nt_rank_metric(const float* scores, const float* targets, const uint8_t* mask, int64_t n, int64_t t,
+                          float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

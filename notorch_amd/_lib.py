@@ -183,7 +183,24 @@ EXT_SIGNATURES: dict[str, tuple] = {
     # the ranking part of RankNContrastLoss (csrc/rnc.hip): sim, dist, n, temp, eps, row_nll, dsim | NULL
     "nt_rnc_max_n": (_c_int, []),
     "nt_rnc_rank": (_c_int, [_vp, _vp, _c_i64, _c_f32, _c_f32, _vp, _vp, _vp]),
+    # the task losses (csrc/task_loss.hip): preds, preds_dtype, targets, mask, sample_weights, lt_mask, gt_mask,
+    # b, t, c, kind, v_kl, eps, loss, dpreds | NULL, workspace, workspace_bytes
+    "nt_task_loss_single_max": (_c_i64, []),
+    "nt_task_loss_workspace": (_c_i64, [_c_i64, _c_i64]),
+    "nt_task_loss": (
+        _c_int,
+        [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_f32, _c_f32, _vp, _vp, _vp,
+         _c_i64, _vp],
+    ),
+    # AUROC / average precision per column (csrc/rank_metric.hip): scores, targets, mask | NULL, n, t, out
+    "nt_rank_metric_max_n": (_c_int, []),
+    "nt_rank_metric": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp]),
 }
+
+# kind codes of nt_task_loss (include/notorch_amd_train.h)
+(NT_LOSS_MSE, NT_LOSS_MAE, NT_LOSS_RMSE, NT_LOSS_BCE, NT_LOSS_MVE, NT_LOSS_EVIDENTIAL, NT_LOSS_XENT) = range(7)
+LOSS_CODES = {"mse": NT_LOSS_MSE, "mae": NT_LOSS_MAE, "rmse": NT_LOSS_RMSE, "bce": NT_LOSS_BCE,
+              "mve": NT_LOSS_MVE, "evidential": NT_LOSS_EVIDENTIAL, "xent": NT_LOSS_XENT}
 
 
 class NativeLibraryError(RuntimeError):

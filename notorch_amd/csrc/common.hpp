@@ -149,6 +149,21 @@ __device__ __forceinline__ void block_max_to(float* p, float a, float b = 0.f, b
   }
 }
 
+// Sum of one value per thread over the workgroup, returned to every thread, in a fixed order: an
+// xor-shuffle tree in each wave, then the wave totals in wave order (red: one slot per wave).  Every
+// thread of the block calls it (two barriers; red is free again on return).
+template <typename V>
+__device__ __forceinline__ V block_sum(V v, V* red) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  V total = red[0];
+  for (int q = 1; q < (int)(blockDim.x >> 6); ++q) total += red[q];
+  __syncthreads();
+  return total;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline int grid_for(int64_t work, int block, int cap = 256 * 16) {

@@ -9,7 +9,7 @@
 // set of k is the suffix that starts where k's tie group starts: a prefix sum of s, a suffix sum of
 // 1 / denom, and the two group bounds.
 //
-// The sort is a fixed bitonic network over P = max(256, next power of two >= n) 64-bit words
+// The sort (sort_scan.hpp, shared with rank_metric.hip) is a fixed bitonic network over P = max(256, next power of two >= n) 64-bit words
 // (key << 32 | column): the key is the bit pattern of D mapped so that unsigned order is descending
 // float order (-0 first made +0, so floats that compare equal have equal keys), the column breaks ties
 // ascending, so all words are distinct, the order is total, and a NaN is just one more bit pattern: the
@@ -23,65 +23,15 @@
 // row, then the dSim row) + 256 B of scan scratch: 48.25 KiB at P = 4096, two workgroups per CU.
 #include "../../include/notorch_amd_train.h"
 #include "common.hpp"
+#include "sort_scan.hpp"
 
 #include <cmath>
 
 namespace nt {
 namespace {
 
-constexpr int kRncMaxN = 4096;  // 4 positions per thread, 1024 threads per workgroup
-constexpr int kRncMinP = 256;
-
-__device__ __forceinline__ uint32_t rnc_desc_key(float d) {
-  const uint32_t u = __float_as_uint(d == 0.f ? 0.f : d);
-  const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~asc;
-}
-
-// compare-exchange of two distinct words: ascending when up
-__device__ __forceinline__ void rnc_cmpx(uint64_t& a, uint64_t& b, bool up) {
-  if ((a > b) == up) {
-    const uint64_t t = a;
-    a = b;
-    b = t;
-  }
-}
-
-struct RncAdd {
-  __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
-};
-struct RncMax {
-  __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; }
-};
-struct RncMin {
-  __device__ __forceinline__ int operator()(int a, int b) const { return a < b ? a : b; }
-};
-
-// Exclusive scan of one value per thread over the workgroup, towards higher threads (REV: towards lower):
-// wave shuffles, one LDS slot per wave, the other waves' totals folded in a fixed order.  Every thread of
-// the block calls it (two barriers; red is free again on return).
-template <typename V, bool REV, typename Op>
-__device__ __forceinline__ V rnc_block_scan(V v, V ident, Op op, V* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  V incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const V t = REV ? __shfl_down(incl, o) : __shfl_up(incl, o);
-    if (REV ? lane + o < 64 : lane >= o) incl = op(incl, t);
-  }
-  V excl = REV ? __shfl_down(incl, 1) : __shfl_up(incl, 1);
-  if (lane == (REV ? 63 : 0)) excl = ident;
-  if (lane == (REV ? 0 : 63)) red[w] = incl;
-  __syncthreads();
-  V pre = ident;
-  if (REV) {
-    for (int q = nw - 1; q > w; --q) pre = op(pre, red[q]);
-  } else {
-    for (int q = 0; q < w; ++q) pre = op(pre, red[q]);
-  }
-  __syncthreads();
-  return op(pre, excl);
-}
+constexpr int kRncMaxN = kSortMaxN;
+constexpr int kRncMinP = kSortMinP;
 
 // VEC: n % 4 == 0 and 16-byte aligned rows (16-byte loads and stores); else by element
 template <bool VEC>
@@ -122,47 +72,7 @@ __global__ __launch_bounds__(1024) void rnc_rank_kernel(const float* __restrict_
     simv[base + e] = sv[e];
     c[e] = ((uint64_t)rnc_desc_key(d[e]) << 32) | (uint32_t)(base + e);
   }
-  // k = 2 and k = 4 of the network: the thread's 4 words sorted, ascending in even threads
-  {
-    const bool up = (tid & 1) == 0;
-    rnc_cmpx(c[0], c[1], up), rnc_cmpx(c[2], c[3], up);
-    rnc_cmpx(c[0], c[2], up), rnc_cmpx(c[1], c[3], up);
-    rnc_cmpx(c[1], c[2], up);
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) comp[base + e] = c[e];
-  __syncthreads();
-
-  // ---- bitonic merges k = 8 .. P
-  for (int k = 8; k <= P; k <<= 1) {
-    int j = k >> 1;
-    // two stages (partner distances j and j / 2) per barrier: the thread's 4 words sit h = j / 2 apart
-    for (; j >= 8; j >>= 2) {
-      const int h = j >> 1, a = ((tid & ~(h - 1)) << 2) | (tid & (h - 1));
-      const bool up = (a & k) == 0;
-      uint64_t w0 = comp[a], w1 = comp[a + h], w2 = comp[a + 2 * h], w3 = comp[a + 3 * h];
-      rnc_cmpx(w0, w2, up), rnc_cmpx(w1, w3, up);
-      rnc_cmpx(w0, w1, up), rnc_cmpx(w2, w3, up);
-      comp[a] = w0, comp[a + h] = w1, comp[a + 2 * h] = w2, comp[a + 3 * h] = w3;
-      __syncthreads();
-    }
-    if (j == 4) {  // an odd number of LDS stages: the last one alone
-      for (int u = tid; u < (P >> 1); u += T) {
-        const int lo = ((u & ~3) << 1) | (u & 3), hi = lo | 4;
-        const uint64_t a = comp[lo], b = comp[hi];
-        if ((a > b) == ((lo & k) == 0)) comp[lo] = b, comp[hi] = a;
-      }
-      __syncthreads();
-    }
-    const bool up = (base & k) == 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c[e] = comp[base + e];
-    rnc_cmpx(c[0], c[2], up), rnc_cmpx(c[1], c[3], up);
-    rnc_cmpx(c[0], c[1], up), rnc_cmpx(c[2], c[3], up);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) comp[base + e] = c[e];
-    __syncthreads();
-  }
+  block_bitonic_sort4(c, comp, P);
 
   // ---- c[] holds sorted positions base .. base + 3: D descending, column ascending among equals
   uint32_t key[4], col[4];

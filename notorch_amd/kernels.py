@@ -53,6 +53,10 @@ __all__ = [
     "softmax_pool_backward_mixed",
     "rnc_max_n",
     "rnc_rank",
+    "task_loss",
+    "task_loss_single_max",
+    "rank_metric",
+    "rank_metric_max_n",
 ]
 
 
@@ -1589,3 +1593,77 @@ def rnc_rank(sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool
     _run(dev, _lib.load().nt_rnc_rank,
          _ptr(sim), _ptr(dist), n, float(temp), float(eps), _ptr(row_nll), _ptr(dsim), _stream(dev))
     return row_nll, dsim
+
+
+# ------------------------------------------------------------------------- task losses and ranking metrics
+def task_loss_single_max() -> int:
+    """Largest b * t that task_loss takes in one launch of one workgroup (the library's constant)."""
+    return int(_lib.load().nt_task_loss_single_max())
+
+
+def _byte_mask(name: str, m: Tensor | None, shape: tuple) -> Tensor | None:
+    """A b x t mask as the bytes nt_task_loss / nt_rank_metric read (torch.bool is one byte per element)."""
+    if m is None:
+        return None
+    if m.dtype != torch.bool:
+        raise TypeError(f"{name} must be a bool tensor, got {m.dtype}")
+    if tuple(m.shape) != shape or not m.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {shape}, got {tuple(m.shape)}")
+    return m.view(torch.uint8)
+
+
+def task_loss(preds: Tensor, targets: Tensor, kind: str, mask: Tensor | None = None,
+              sample_weights: Tensor | None = None, lt_mask: Tensor | None = None, gt_mask: Tensor | None = None,
+              v_kl: float = 0.0, eps: float = 0.0, need_grad: bool = False) -> tuple[Tensor, Tensor | None]:
+    """The element loss ``kind`` (a key of _lib.LOSS_CODES), its masked weighted reduction and, with need_grad,
+    dLoss/dpreds from the same launch (nt_task_loss): preds b x t [x c] fp32 or bf16, targets b x t fp32, mask /
+    lt_mask / gt_mask b x t bool, sample_weights b fp32.  Returns (loss, a 0-d fp32 tensor; dpreds in the dtype
+    of preds, or None: no gradient buffer is allocated)."""
+    dev = _require_device(preds, targets, mask, sample_weights, lt_mask, gt_mask)
+    code = _require_feat("preds", preds)
+    _require_f32("targets", targets)
+    if kind not in _lib.LOSS_CODES:
+        raise ValueError(f"unknown loss kind {kind!r} (one of {sorted(_lib.LOSS_CODES)})")
+    if targets.dim() != 2 or preds.dim() not in (2, 3) or tuple(preds.shape[:2]) != tuple(targets.shape):
+        raise ValueError(f"preds must be b x t [x c] and targets b x t, got {tuple(preds.shape)} and "
+                         f"{tuple(targets.shape)}")
+    b, t = targets.shape
+    c = preds.shape[2] if preds.dim() == 3 else 1
+    shape = (b, t)
+    masks = [_byte_mask(n, m, shape) for n, m in (("mask", mask), ("lt_mask", lt_mask), ("gt_mask", gt_mask))]
+    if sample_weights is not None:
+        _require_f32("sample_weights", sample_weights)
+        if tuple(sample_weights.shape) != (b,):
+            raise ValueError(f"sample_weights must have shape ({b},), got {tuple(sample_weights.shape)}")
+    lib = _lib.load()
+    loss = torch.full((), float("nan"), dtype=torch.float32, device=dev) if b * t == 0 else \
+        torch.empty((), dtype=torch.float32, device=dev)
+    dpreds = torch.empty_like(preds) if need_grad else None
+    ws_bytes = int(lib.nt_task_loss_workspace(b, t))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    _run(dev, lib.nt_task_loss,
+         _ptr(preds), code, _ptr(targets), _ptr(masks[0]), _ptr(sample_weights), _ptr(masks[1]), _ptr(masks[2]),
+         b, t, c, _lib.LOSS_CODES[kind], float(v_kl), float(eps), _ptr(loss), _ptr(dpreds), _ptr(ws), ws_bytes,
+         _stream(dev))
+    return loss, dpreds
+
+
+def rank_metric_max_n() -> int:
+    """Largest n of rank_metric (what one workgroup's LDS and threads hold; the library's constant)."""
+    return int(_lib.load().nt_rank_metric_max_n())
+
+
+def rank_metric(scores: Tensor, targets: Tensor, mask: Tensor | None = None) -> Tensor:
+    """AUROC, average precision, P and N of every column of n x t fp32 scores and targets (nt_rank_metric): a
+    t x 4 fp32 tensor.  An entry counts as positive where int(target) == 1, negative where it is 0, and is ignored
+    otherwise or where the n x t bool mask is False; AUROC and AP are NaN for a column without both classes."""
+    dev = _require_device(scores, targets, mask)
+    _require_f32("scores", scores)
+    _require_f32("targets", targets)
+    if scores.dim() != 2 or scores.shape != targets.shape:
+        raise ValueError(f"scores and targets must be n x t, got {tuple(scores.shape)} and {tuple(targets.shape)}")
+    n, t = scores.shape
+    m = _byte_mask("mask", mask, (n, t))
+    out = torch.empty(t, 4, dtype=torch.float32, device=dev)
+    _run(dev, _lib.load().nt_rank_metric, _ptr(scores), _ptr(targets), _ptr(m), n, t, _ptr(out), _stream(dev))
+    return out

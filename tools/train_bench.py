@@ -25,11 +25,17 @@ the unfused path it spans the update and the dropout kernel, not the segment red
 Sum; with --autocast it runs inside the region on the block's bf16 node_feats (nt_node_scores_mixed,
 nt_softmax_pool_backward_mixed).  --readout gated-f32 is the A/B for that: node_feats widened to fp32 by
 torch and the readout on the fp32 kernels outside the region, what mixed precision had to run before.
+--loss mse|mve|evidential closes the step with a task head and a real loss in place of out.pow(2).sum(): an
+nn.Linear(h, tasks * c) on the readout (c = 1, 2, 4; softplus on the variance-like channels: v + 0.1,
+alpha + 1, beta + 0.1), then notorch_amd.nn.loss.MSE / MVE / Evidential against fixed randn targets.  The head
+is in the optimizer.  The loss takes the kernel (nt_task_loss, one launch for loss and gradient) or, with
+NT_LOSS=torch in the environment, torch ops under autograd; the JSON names the route.
 The table and the JSON also report torch.cuda.max_memory_allocated over the timed steps.
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
                                   [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--autocast]
-                                  [--dropout P] [--readout sum|gated|gated-f32] [--json]"""
+                                  [--dropout P] [--readout sum|gated|gated-f32]
+                                  [--loss mse|mve|evidential [--tasks 1]] [--json]"""
 import argparse
 import contextlib
 import json
@@ -78,6 +84,10 @@ def main():
                    help="sum: the Sum readout; gated: a trained Gated readout on the block's output as it is "
                         "(under --autocast: bf16 rows, fp32 keys, inside the region); gated-f32: the same readout "
                         "on node_feats.float(), outside the autocast region")
+    p.add_argument("--loss", default=None, choices=["mse", "mve", "evidential"],
+                   help="close the step with an nn.Linear(h, tasks * c) head and this loss (NT_LOSS=torch: the torch-ops "
+                        "route) in place of out.pow(2).sum()")
+    p.add_argument("--tasks", type=int, default=1, help="with --loss: the number of target columns t")
     p.add_argument("--json", action="store_true", help="print one JSON object instead of the table")
     a = p.parse_args()
     if a.autocast and a.dtype != "f32":
@@ -107,9 +117,28 @@ def main():
         blk = ChempropBlock(a.h, depth=a.depth, dropout=a.dropout).to("cuda", dt).train()
         Xv_d = Gd.node_feats.requires_grad_(True)
         Xe_d = Gd.edge_feats.requires_grad_(True)
+    head = crit = None
+    if a.loss:
+        from notorch_amd.nn import loss as losses
+
+        c = {"mse": 1, "mve": 2, "evidential": 4}[a.loss]
+        head = torch.nn.Linear(a.h, a.tasks * c).to("cuda", dt).train()
+        crit = {"mse": losses.MSE, "mve": losses.MVE, "evidential": losses.Evidential}[a.loss]()
+        targets = torch.randn(a.mols, a.tasks, device="cuda")
+        shift = torch.tensor([0.0, 0.1, 1.0, 0.1][:c], device="cuda")[1:]
+
+    def task_loss(x):
+        if head is None:
+            return x.float().pow(2).sum()
+        out = head(x).view(a.mols, a.tasks, -1)
+        if out.shape[-1] == 1:
+            return crit(out.squeeze(-1), targets)
+        wide = torch.nn.functional.softplus(out[..., 1:]) + shift.to(out.dtype)
+        return crit(torch.cat([out[..., :1], wide], -1), targets)
+
     opt = None
     if a.optim != "none":
-        opt = torch.optim.Adam([*blk.parameters(), *ro.parameters()], lr=1e-4,
+        opt = torch.optim.Adam([*blk.parameters(), *ro.parameters(), *(head.parameters() if head else ())], lr=1e-4,
                                **({"fused": True} if a.optim == "adam-fused" else {}))
 
     def read(out):
@@ -121,13 +150,15 @@ def main():
     def step():
         blk.zero_grad(set_to_none=True)
         ro.zero_grad(set_to_none=True)
+        if head is not None:
+            head.zero_grad(set_to_none=True)
         with region():
             if a.embedded:
                 out = blk(Gd)
             else:
                 Xv_d.grad = Xe_d.grad = None
                 out = blk(Gd.update(node_feats=Xv_d, edge_feats=Xe_d))
-            loss = read(out).float().pow(2).sum()
+            loss = task_loss(read(out))
         loss.backward()
         if opt is not None:
             opt.step()
@@ -183,6 +214,9 @@ def main():
             **({"embedded": True, "embed_bwd": a.embed_bwd} if a.embedded else {}),
             **({"autocast": "bf16"} if a.autocast else {}),
             **({"readout": a.readout} if a.readout != "sum" else {}),
+            **({"loss": a.loss, "tasks": a.tasks,
+                "loss_route": "kernel" if crit._kernel_route(torch.empty(1, 1, device="cuda", dtype=dt),
+                                                             targets[:1, :1]) else "torch"} if a.loss else {}),
             **layer,
             "max_memory_allocated": mem,
             "warmup": a.warmup, "steps": a.steps,
@@ -192,6 +226,7 @@ def main():
     print(f"{a.kind} V={G.num_nodes} E={E} h={a.h} depth={a.depth} {a.dtype} optim={a.optim}"
           + (f" embedded embed-bwd={a.embed_bwd}" if a.embedded else "") + (" autocast=bf16" if a.autocast else "")
           + (f" readout={a.readout}" if a.readout != "sum" else "")
+          + (f" loss={a.loss} tasks={a.tasks} NT_LOSS={os.environ.get('NT_LOSS', '') or 'default'}" if a.loss else "")
           + (f" dropout={a.dropout} layer {layer['layer_us']:.1f} us: {layer['layer_kernel']}" if layer else ""))
     for k, v in res.items():
         print(f"{k:14s} {v:8.3f} ms/step  {E * a.depth / (v * 1e-3):.3e} edge-msg/s  "
