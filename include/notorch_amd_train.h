@@ -231,6 +231,37 @@ NT_API int nt_rank_metric_max_n(void);
 NT_API int nt_rank_metric(const float* scores, const float* targets, const uint8_t* mask, int64_t n, int64_t t,
                           float* out, void* stream);
 
+/*
+ * nt_rank_metric for columns of any n up to nt_rank_metric_long_max_n() = 2^24 (P and N return as fp32
+ * counts, exact up to 2^24): same arguments, label rule, formulas and output layout, on several workgroups
+ * per column (csrc/rank_metric_long.hip).  With tile = 4096 positions and tiles = ceil(n / 4096), one call is
+ * a fixed chain of 5 + ceil(log2 tiles) launches on the caller's stream:
+ *   runs     one workgroup per (tile, column) sorts its 4096 words (nt_rank_metric's word with the global
+ *            row, so all words of a column are distinct; padding counts on past n behind every score);
+ *   merge    ceil(log2 tiles) passes between two word buffers: neighbouring sorted sequences of length L
+ *            become one of length 2 L, one workgroup per 4096-word output tile, split by merge path;
+ *   scan     tile partials (total counts, the local counts at the tile's last end of a group of equal
+ *            scores), then per column the carries (the exclusive prefix of the totals; the counts at the
+ *            latest group end before the tile), then every tile's AUROC and AP terms from those carries,
+ *            then per column their sum: the integers exactly, the fp64 terms in a fixed order.
+ * Every ordering between workgroups is a launch boundary: no workgroup waits for another inside a launch,
+ * and there are no floating-point atomics; two calls return the same bits, whatever the workspace held.
+ * Stream-ordered: no synchronisation, no allocation.  AUROC, P and N have the bits nt_rank_metric returns
+ * where both take n; AP is the same fp64 sum in another fixed order.
+ * workspace: nt_rank_metric_long_workspace(n, t) = tiles * t * (2 * 32768 + 48) bytes of caller-owned device
+ * memory, 16-byte aligned (two word buffers; partials, carries and terms); the query answers -1 for sizes
+ * the call refuses.
+ * Checked on the host before any device call, in this order: NULL scores / targets / out (NT_EINVAL);
+ * n < 0, t < 0, t >= 2^31 or tiles * t >= 2^31 (NT_EINVAL, "bad sizes"); n > nt_rank_metric_long_max_n()
+ * (NT_EUNSUPPORTED); t == 0 launches nothing (NT_OK); n == 0 writes NaN, NaN, 0, 0 per column and reads no
+ * workspace; otherwise a NULL, misaligned or short workspace (NT_EINVAL).
+ */
+NT_API int64_t nt_rank_metric_long_max_n(void);
+/* bytes of workspace for these sizes; -1 for bad sizes */
+NT_API int64_t nt_rank_metric_long_workspace(int64_t n, int64_t t);
+NT_API int nt_rank_metric_long(const float* scores, const float* targets, const uint8_t* mask, int64_t n,
+                               int64_t t, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,10 @@ EXT_SIGNATURES: dict[str, tuple] = {
     # AUROC / average precision per column (csrc/rank_metric.hip): scores, targets, mask | NULL, n, t, out
     "nt_rank_metric_max_n": (_c_int, []),
     "nt_rank_metric": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp]),
+    # the same above one workgroup's 4096 rows (csrc/rank_metric_long.hip): ... out, workspace, workspace_bytes
+    "nt_rank_metric_long_max_n": (_c_i64, []),
+    "nt_rank_metric_long_workspace": (_c_i64, [_c_i64, _c_i64]),
+    "nt_rank_metric_long": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp]),
 }
 
 # kind codes of nt_task_loss (include/notorch_amd_train.h)

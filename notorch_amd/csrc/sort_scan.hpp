@@ -1,5 +1,6 @@
 // One workgroup sorts and scans a row in LDS: the fixed bitonic network and the block scan shared by the
-// Rank-N-Contrast kernel (rnc.hip) and the ranking metrics (rank_metric.hip).
+// Rank-N-Contrast kernel (rnc.hip) and the ranking metrics (rank_metric.hip; rank_metric_long.hip sorts its
+// runs with it and merges them with the network's last iteration, block_bitonic_merge4).
 //
 // The network runs over P = a power of two >= 256 64-bit words, (key << 32 | payload), in P / 4 threads
 // (at most 1024, so P <= 4096): each thread owns 4 consecutive sorted positions, the stages with partner
@@ -118,6 +119,35 @@ __device__ __forceinline__ void block_bitonic_sort4(uint64_t (&c)[4], uint64_t* 
     for (int e = 0; e < 4; ++e) comp[base + e] = c[e];
     __syncthreads();
   }
+}
+
+// The k = P iteration of the network above on its own: comp[0 .. P) (LDS) holds a BITONIC sequence (ascending,
+// then descending: two sorted runs, the second reversed) and every thread has passed a barrier; on return c[e]
+// is the ascending sorted word of position 4 * threadIdx.x + e.  comp is left mid-network (not rewritten after
+// the register stages).  blockDim.x == P / 4; every thread of the block calls it.  6 barriers at P = 4096.
+__device__ __forceinline__ void block_bitonic_merge4(uint64_t (&c)[4], uint64_t* comp, int P) {
+  const int tid = threadIdx.x, T = blockDim.x, base = 4 * tid;
+  int j = P >> 1;
+  for (; j >= 8; j >>= 2) {
+    const int h = j >> 1, a = ((tid & ~(h - 1)) << 2) | (tid & (h - 1));
+    uint64_t w0 = comp[a], w1 = comp[a + h], w2 = comp[a + 2 * h], w3 = comp[a + 3 * h];
+    rnc_cmpx(w0, w2, true), rnc_cmpx(w1, w3, true);
+    rnc_cmpx(w0, w1, true), rnc_cmpx(w2, w3, true);
+    comp[a] = w0, comp[a + h] = w1, comp[a + 2 * h] = w2, comp[a + 3 * h] = w3;
+    __syncthreads();
+  }
+  if (j == 4) {
+    for (int u = tid; u < (P >> 1); u += T) {
+      const int lo = ((u & ~3) << 1) | (u & 3), hi = lo | 4;
+      const uint64_t a = comp[lo], b = comp[hi];
+      if (a > b) comp[lo] = b, comp[hi] = a;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) c[e] = comp[base + e];
+  rnc_cmpx(c[0], c[2], true), rnc_cmpx(c[1], c[3], true);
+  rnc_cmpx(c[0], c[1], true), rnc_cmpx(c[2], c[3], true);
 }
 
 }  // namespace nt

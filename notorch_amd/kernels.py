@@ -56,6 +56,8 @@ __all__ = [
     "task_loss",
     "task_loss_single_max",
     "rank_metric",
+    "rank_metric_long",
+    "rank_metric_long_max_n",
     "rank_metric_max_n",
 ]
 
@@ -1666,4 +1668,34 @@ def rank_metric(scores: Tensor, targets: Tensor, mask: Tensor | None = None) -> 
     m = _byte_mask("mask", mask, (n, t))
     out = torch.empty(t, 4, dtype=torch.float32, device=dev)
     _run(dev, _lib.load().nt_rank_metric, _ptr(scores), _ptr(targets), _ptr(m), n, t, _ptr(out), _stream(dev))
+    return out
+
+
+def rank_metric_long_max_n() -> int:
+    """Largest n of rank_metric_long (P and N return as fp32 counts, exact up to 2^24; the library's constant)."""
+    return int(_lib.load().nt_rank_metric_long_max_n())
+
+
+def rank_metric_long(scores: Tensor, targets: Tensor, mask: Tensor | None = None,
+                     workspace: Tensor | None = None) -> Tensor:
+    """rank_metric for any n up to rank_metric_long_max_n() (nt_rank_metric_long): sorted runs of 4096 rows,
+    merge passes and a tiled scan over several workgroups per column.  ``workspace`` is a contiguous uint8
+    device tensor of at least nt_rank_metric_long_workspace(n, t) bytes, 16-byte aligned (its contents do not
+    matter); without one the call allocates it."""
+    dev = _require_device(scores, targets, mask, workspace)
+    _require_f32("scores", scores)
+    _require_f32("targets", targets)
+    if scores.dim() != 2 or scores.shape != targets.shape:
+        raise ValueError(f"scores and targets must be n x t, got {tuple(scores.shape)} and {tuple(targets.shape)}")
+    n, t = scores.shape
+    m = _byte_mask("mask", mask, (n, t))
+    lib = _lib.load()
+    ws_bytes = int(lib.nt_rank_metric_long_workspace(n, t))
+    if workspace is None:
+        workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise TypeError(f"workspace must be a contiguous uint8 tensor, got {workspace.dtype}")
+    out = torch.empty(t, 4, dtype=torch.float32, device=dev)
+    _run(dev, lib.nt_rank_metric_long, _ptr(scores), _ptr(targets), _ptr(m), n, t, _ptr(out), _ptr(workspace),
+         0 if workspace is None else workspace.numel(), _stream(dev))
     return out

@@ -12,10 +12,13 @@ negative where it is 0, ignored otherwise or where ``mask`` is False; ``mask=Non
 AUROC is the trapezoid over distinct thresholds (Mann-Whitney, ties counted half), AUPRC the average
 precision ``sum_g (tp_g - tp_{g-1}) / P * tp_g / (tp_g + fp_g)`` over the groups ``g`` of equal scores.
 
-* **kernel**: fp32 / bf16 / fp16 scores on a ROCm device with at most ``kernels.rank_metric_max_n()``
-  ranked rows: ``nt_rank_metric``, one workgroup per column.  Metrics carry no gradient.
+* **kernel**: fp32 / bf16 / fp16 scores on a ROCm device.  Up to ``kernels.rank_metric_max_n()`` (4096) ranked
+  rows: ``nt_rank_metric``, one workgroup per column.  Above that, up to ``RANK_LONG_DEFAULT_MAX_N`` rows
+  (with ``NT_LOSS=kernel``: up to ``kernels.rank_metric_long_max_n()`` = 2^24): ``nt_rank_metric_long``, sorted
+  runs of 4096 rows, merge passes and a tiled scan over several workgroups per column.  Metrics carry no
+  gradient.
 * **torch ops**: a sort, cumulative sums and the group ends (never ``O(n^2)``), on any device and dtype:
-  CPU, fp64, more rows, or ``NT_LOSS=torch`` in the environment (read per call).
+  CPU, fp64, more rows than the above, or ``NT_LOSS=torch`` in the environment (read per call).
 
 ``R2``, ``Accuracy`` and ``F1`` are torch ops on every device.
 """
@@ -32,7 +35,12 @@ from notorch_amd import kernels as K
 from notorch_amd.nn.loss.loss import _as_bool, _BoundedMixin, _LossFunctionBase
 
 __all__ = ["MAE", "RMSE", "BoundedMAE", "BoundedRMSE", "R2", "AUROC", "AUPRC", "Accuracy", "F1",
-           "rank_metric_torch"]
+           "rank_metric_torch", "RANK_LONG_DEFAULT_MAX_N"]
+
+# Rankings of more than kernels.rank_metric_max_n() and at most this many rows take nt_rank_metric_long without
+# being asked to (NT_LOSS=kernel: up to kernels.rank_metric_long_max_n()).  The largest n timed such that the
+# kernel is not slower than the torch route there and at every smaller n timed: DESIGN.md section 4.
+RANK_LONG_DEFAULT_MAX_N = 1 << 20
 
 
 class MAE(_LossFunctionBase):
@@ -129,7 +137,8 @@ class _RankMetric(_ClassificationMetricBase):
             raise ValueError(f"task={self.task} ranks the columns of b x t scores, got {tuple(preds.shape)}")
         if self._kernel_route(preds, targets, mask):
             mk = None if mask is None else _as_bool(mask).contiguous()
-            res = K.rank_metric(preds.detach().float().contiguous(), targets.detach().float().contiguous(), mk)
+            kernel = K.rank_metric if preds.shape[0] <= K.rank_metric_max_n() else K.rank_metric_long
+            res = kernel(preds.detach().float().contiguous(), targets.detach().float().contiguous(), mk)
         else:
             res = rank_metric_torch(preds, targets, mask)
         vals = res[:, self.COLUMN]
@@ -143,9 +152,13 @@ class _RankMetric(_ClassificationMetricBase):
             return False
         if any(x is not None and x.device != preds.device for x in (targets, mask)):
             return False
-        if os.environ.get("NT_LOSS", "") == "torch":
+        knob = os.environ.get("NT_LOSS", "")
+        if knob == "torch":
             return False
-        return preds.shape[0] <= K.rank_metric_max_n()
+        n = preds.shape[0]
+        if n <= K.rank_metric_max_n():
+            return True
+        return n <= (K.rank_metric_long_max_n() if knob == "kernel" else RANK_LONG_DEFAULT_MAX_N)
 
 
 class AUROC(_RankMetric):
