@@ -167,6 +167,19 @@ NT_API int nt_rnc_rank(const float* sim, const float* dist, int64_t n, float tem
                        float* dsim, void* stream);
 
 /*
+ * nt_rnc_rank for longer rows (csrc/rnc_long.hip; additive to ABI 8): the same arguments, results, host
+ * checks and guarantees, for 0 <= n <= nt_rnc_long_max_n() = 16384.  Still one workgroup per row, with 8
+ * sorted positions per thread up to n = 8192 and 16 above, in 8 P + 256 bytes of LDS (P = max(512, next
+ * power of two >= n): 64.25 KiB at 8192, 128.25 KiB at 16384, set with the dynamic-LDS attribute).  The
+ * sums run in an order fixed by (n, position) that differs from nt_rnc_rank's in the per-thread part, so the
+ * two agree to fp32 rounding, not bit for bit.  n > nt_rnc_long_max_n() is NT_EUNSUPPORTED.  One launch,
+ * no allocation, no synchronisation.
+ */
+NT_API int nt_rnc_long_max_n(void);
+NT_API int nt_rnc_rank_long(const float* sim, const float* dist, int64_t n, float temp, float eps,
+                            float* row_nll, float* dsim, void* stream);
+
+/*
  * The task losses and regression metrics of notorch/nn/loss/loss.py and notorch/nn/metrics.py: element
  * loss, masked weighted reduction and the gradient of the reduced loss (csrc/task_loss.hip).
  *

@@ -183,6 +183,9 @@ EXT_SIGNATURES: dict[str, tuple] = {
     # the ranking part of RankNContrastLoss (csrc/rnc.hip): sim, dist, n, temp, eps, row_nll, dsim | NULL
     "nt_rnc_max_n": (_c_int, []),
     "nt_rnc_rank": (_c_int, [_vp, _vp, _c_i64, _c_f32, _c_f32, _vp, _vp, _vp]),
+    # the same for rows above nt_rnc_max_n(), up to nt_rnc_long_max_n() (csrc/rnc_long.hip)
+    "nt_rnc_long_max_n": (_c_int, []),
+    "nt_rnc_rank_long": (_c_int, [_vp, _vp, _c_i64, _c_f32, _c_f32, _vp, _vp, _vp]),
     # the task losses (csrc/task_loss.hip): preds, preds_dtype, targets, mask, sample_weights, lt_mask, gt_mask,
     # b, t, c, kind, v_kl, eps, loss, dpreds | NULL, workspace, workspace_bytes
     "nt_task_loss_single_max": (_c_i64, []),

@@ -150,4 +150,82 @@ __device__ __forceinline__ void block_bitonic_merge4(uint64_t (&c)[4], uint64_t*
   rnc_cmpx(c[0], c[1], true), rnc_cmpx(c[2], c[3], true);
 }
 
+// ---- wide rows (rnc_long.hip): the same network with E = 8 or 16 consecutive positions per thread, so
+// P = E * blockDim.x reaches 8192 or 16384.  The stages with partner distance < E run in registers on the
+// thread's own words; the others go through LDS, log2(E) stages between two barriers.
+
+// The stages with partner distances G / 2 .. 1 of one merge on G words in registers, all in direction up.
+template <int G>
+__device__ __forceinline__ void rnc_reg_stages(uint64_t (&w)[G], bool up) {
+#pragma unroll
+  for (int d = G / 2; d >= 1; d >>= 1) {
+#pragma unroll
+    for (int m = 0; m < G; ++m)
+      if ((m & d) == 0) rnc_cmpx(w[m], w[m | d], up);
+  }
+}
+
+// NS stages of merge k (partner distances j, j / 2, .., h = j >> (NS - 1)) on comp[0 .. E * blockDim.x),
+// then a barrier.  A thread takes E >> NS groups of 2^NS words that sit h apart, which are exactly the
+// words those stages connect.  k >= 2 j, so the direction is the same for the whole group.
+template <int E, int NS>
+__device__ __forceinline__ void rnc_lds_stages(uint64_t* comp, int k, int j) {
+  constexpr int G = 1 << NS;
+  const int h = j >> (NS - 1);
+#pragma unroll
+  for (int g = 0; g < E / G; ++g) {
+    const int u = (int)threadIdx.x + g * (int)blockDim.x;
+    const int a = ((u & ~(h - 1)) << NS) | (u & (h - 1));
+    uint64_t w[G];
+#pragma unroll
+    for (int m = 0; m < G; ++m) w[m] = comp[a + m * h];
+    rnc_reg_stages<G>(w, (a & k) == 0);
+#pragma unroll
+    for (int m = 0; m < G; ++m) comp[a + m * h] = w[m];
+  }
+  __syncthreads();
+}
+
+// Sorts the P = E * blockDim.x words of the workgroup ascending: c[e] is the word of position
+// E * threadIdx.x + e on entry and the sorted word of that position on return.  comp[0 .. P) (LDS) is left
+// mid-network and NO barrier follows the last read of it: the caller places one before it reuses comp.
+// P >= 2 E; every thread of the block calls it.  Barriers: 32 at P = 8192 (E = 8), 28 at P = 16384 (E = 16).
+template <int E>
+__device__ __forceinline__ void block_bitonic_sort_wide(uint64_t (&c)[E], uint64_t* comp, int P) {
+  static_assert(E == 8 || E == 16, "8 or 16 positions per thread");
+  constexpr int S = E == 16 ? 4 : 3;  // log2(E): LDS stages between two barriers
+  const int tid = threadIdx.x, base = E * tid;
+  // k = 2 .. E of the network: the thread's words sorted, ascending in even threads
+#pragma unroll
+  for (int k = 2; k <= E; k <<= 1) {
+#pragma unroll
+    for (int d = k / 2; d >= 1; d >>= 1) {
+#pragma unroll
+      for (int m = 0; m < E; ++m)
+        if ((m & d) == 0) rnc_cmpx(c[m], c[m | d], k < E ? (m & k) == 0 : (tid & 1) == 0);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < E; ++e) comp[base + e] = c[e];
+  __syncthreads();
+
+  // ---- bitonic merges k = 2 E .. P: `stages` partner distances k / 2 .. E through LDS, the rest in registers
+  int stages = 1;
+  for (int k = 2 * E; k <= P; k <<= 1, ++stages) {
+    int j = k >> 1, left = stages;
+    for (; left >= S; left -= S, j >>= S) rnc_lds_stages<E, S>(comp, k, j);
+    if (left == 1) rnc_lds_stages<E, 1>(comp, k, j);
+    if (left == 2) rnc_lds_stages<E, 2>(comp, k, j);
+    if (S == 4 && left == 3) rnc_lds_stages<E, 3>(comp, k, j);
+#pragma unroll
+    for (int e = 0; e < E; ++e) c[e] = comp[base + e];
+    rnc_reg_stages<E>(c, (base & k) == 0);
+    if (k < P) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) comp[base + e] = c[e];
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace nt

@@ -53,6 +53,8 @@ __all__ = [
     "softmax_pool_backward_mixed",
     "rnc_max_n",
     "rnc_rank",
+    "rnc_long_max_n",
+    "rnc_rank_long",
     "task_loss",
     "task_loss_single_max",
     "rank_metric",
@@ -1580,10 +1582,8 @@ def rnc_max_n() -> int:
     return int(_lib.load().nt_rnc_max_n())
 
 
-def rnc_rank(sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool) -> tuple[Tensor, Tensor | None]:
-    """The ranking part of RankNContrastLoss for n x n fp32 sim and dist (nt_rnc_rank): row_nll[i] =
-    sum_{j != i} (log denom_ij - sim_ij / temp) and, with need_grad, dsim = d(mean loss) / d sim from
-    the same launch (else None: no n x n buffer is allocated)."""
+def _rnc_rank(entry: str, sim: Tensor, dist: Tensor, temp: float, eps: float,
+              need_grad: bool) -> tuple[Tensor, Tensor | None]:
     dev = _require_device(sim, dist)
     _require_f32("sim", sim)
     _require_f32("dist", dist)
@@ -1592,9 +1592,28 @@ def rnc_rank(sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool
     n = sim.shape[0]
     row_nll = torch.empty(n, dtype=torch.float32, device=dev)
     dsim = torch.empty_like(sim) if need_grad else None
-    _run(dev, _lib.load().nt_rnc_rank,
+    _run(dev, getattr(_lib.load(), entry),
          _ptr(sim), _ptr(dist), n, float(temp), float(eps), _ptr(row_nll), _ptr(dsim), _stream(dev))
     return row_nll, dsim
+
+
+def rnc_rank(sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool) -> tuple[Tensor, Tensor | None]:
+    """The ranking part of RankNContrastLoss for n x n fp32 sim and dist (nt_rnc_rank): row_nll[i] =
+    sum_{j != i} (log denom_ij - sim_ij / temp) and, with need_grad, dsim = d(mean loss) / d sim from
+    the same launch (else None: no n x n buffer is allocated)."""
+    return _rnc_rank("nt_rnc_rank", sim, dist, temp, eps, need_grad)
+
+
+def rnc_long_max_n() -> int:
+    """Largest n of rnc_rank_long (16 positions per thread in 128.25 KiB of LDS; the library's constant)."""
+    return int(_lib.load().nt_rnc_long_max_n())
+
+
+def rnc_rank_long(sim: Tensor, dist: Tensor, temp: float, eps: float,
+                  need_grad: bool) -> tuple[Tensor, Tensor | None]:
+    """rnc_rank for n up to rnc_long_max_n() (nt_rnc_rank_long): the same arguments and results, equal to
+    rnc_rank's to fp32 rounding (the per-thread part of the sums has another, equally fixed, order)."""
+    return _rnc_rank("nt_rnc_rank_long", sim, dist, temp, eps, need_grad)
 
 
 # ------------------------------------------------------------------------- task losses and ranking metrics

@@ -9,12 +9,17 @@ The reference materialises the ``N x N x N`` mask of the comparison.  Here every
 label distances (descending): the ``>=`` set of ``j`` is then the prefix of the row that ends where j's
 group of equal distances ends, so one prefix sum of ``s`` per row serves every ``j``: O(N^2) memory.
 
-Two routes, chosen without a device-to-host copy (``N`` comes from the shape):
+Three routes, chosen by ``rnc_route`` without a device-to-host copy (``N`` comes from the shape):
 
 * fp32 (or bf16 / fp16, widened) ``Sim`` and ``D`` on a ROCm device with ``N <= kernels.rnc_max_n()``:
   the HIP kernel ``nt_rnc_rank``, one workgroup per row, which under grad also writes ``dLoss/dSim``;
-* anything else (CPU tensors, fp64, larger ``N``, or ``NT_RNC=torch`` in the environment, read per
-  call): the same sorted formulation in torch ops, differentiated by autograd.
+* the same tensors with ``N`` above that and up to ``RNC_LONG_DEFAULT_MAX_N`` (set from
+  ``tools/rnc_bench.py``; up to ``kernels.rnc_long_max_n()`` with ``NT_RNC=kernel``): ``nt_rnc_rank_long``,
+  the same kernel with 8 or 16 sorted positions per thread;
+* anything else (CPU tensors, fp64, larger ``N``, or ``NT_RNC=torch``): the same sorted formulation in
+  torch ops, differentiated by autograd.
+
+``NT_RNC`` is read from the environment per call.
 
 ``k = i`` is inside the sum exactly when ``D[i,j] <= D[i,i]`` (duplicated targets), as in the reference.
 One deliberate difference: the loss is evaluated as ``log denom - Sim / temp``, which stays finite where
@@ -32,7 +37,14 @@ from torch import Tensor
 
 from notorch_amd import kernels as K
 
-__all__ = ["RankNContrastLoss", "CDist", "PNorm", "RnCRankFunction"]
+__all__ = ["RankNContrastLoss", "CDist", "PNorm", "RnCRankFunction", "RnCRankLongFunction", "rnc_route",
+           "RNC_LONG_DEFAULT_MAX_N"]
+
+# Largest N that takes nt_rnc_rank_long without NT_RNC=kernel: the largest N timed by tools/rnc_bench.py at
+# which, as at every smaller timed N, the kernel's median is below the torch route's by more than the torch
+# route's spread over the rounds; 0 would mean no N.  Measured: the kernel is 5 to 11 times
+# ahead at every timed N up to kernels.rnc_long_max_n().
+RNC_LONG_DEFAULT_MAX_N = 16384
 
 
 class CDist(nn.Module):
@@ -89,6 +101,17 @@ class RnCRankFunction(torch.autograd.Function):
         return grad_out * dsim, None, None, None, None
 
 
+class RnCRankLongFunction(RnCRankFunction):
+    """``RnCRankFunction`` on ``K.rnc_rank_long``: N above ``K.rnc_max_n()``, up to ``K.rnc_long_max_n()``."""
+
+    @staticmethod
+    def forward(ctx, sim: Tensor, dist: Tensor, temp: float, eps: float, need_grad: bool) -> Tensor:
+        n = sim.shape[0]
+        row_nll, dsim = K.rnc_rank_long(sim, dist, temp, eps, need_grad)
+        ctx.save_for_backward(dsim)
+        return row_nll.sum() / (n * (n - 1))
+
+
 def rank_loss_torch(sim: Tensor, dist: Tensor, temp: float, eps: float) -> Tensor:
     """The sorted formulation in torch ops (any device and dtype; autograd differentiates it)."""
     n = sim.shape[0]
@@ -104,6 +127,22 @@ def rank_loss_torch(sim: Tensor, dist: Tensor, temp: float, eps: float) -> Tenso
     nll = denom.log() - logits
     diag = torch.eye(n, dtype=torch.bool, device=sim.device)
     return nll.masked_fill(diag, 0.0).sum() / (n * (n - 1))
+
+
+_NARROW = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def rnc_route(n: int, device_type: str, sim_dtype: torch.dtype, dist_dtype: torch.dtype, knob: str) -> str:
+    """Which route an N x N problem takes: ``"kernel"`` (``nt_rnc_rank``), ``"long"`` (``nt_rnc_rank_long``)
+    or ``"torch"``.  ``knob`` is the value of ``NT_RNC``: ``"torch"`` forces torch, ``"kernel"`` takes the
+    kernels as far as they reach instead of as far as they were measured to win."""
+    if device_type != "cuda" or sim_dtype not in _NARROW or dist_dtype not in _NARROW or knob == "torch":
+        return "torch"
+    if n <= K.rnc_max_n():
+        return "kernel"
+    if n <= (K.rnc_long_max_n() if knob == "kernel" else RNC_LONG_DEFAULT_MAX_N):
+        return "long"
+    return "torch"
 
 
 class RankNContrastLoss(nn.Module):
@@ -122,20 +161,14 @@ class RankNContrastLoss(nn.Module):
         sims = self.similarity(inputs)
         if N < 2:  # the mean over no pairs
             return torch.full((), float("nan"), dtype=sims.dtype, device=sims.device)
-        if self._kernel_route(sims, dists, N):
-            sims = sims.float().contiguous()
-            return RnCRankFunction.apply(sims, dists.detach().float().contiguous(), float(self.temp), self.EPS,
-                                         torch.is_grad_enabled() and sims.requires_grad)
-        return rank_loss_torch(sims, dists, self.temp, self.EPS)
-
-    @staticmethod
-    def _kernel_route(sims: Tensor, dists: Tensor, N: int) -> bool:
-        narrow = (torch.float32, torch.bfloat16, torch.float16)
-        if not (sims.is_cuda and dists.is_cuda and sims.dtype in narrow and dists.dtype in narrow):
-            return False
-        if os.environ.get("NT_RNC", "") == "torch":
-            return False
-        return N <= K.rnc_max_n()
+        device = "cuda" if sims.is_cuda and dists.is_cuda else "cpu"
+        route = rnc_route(N, device, sims.dtype, dists.dtype, os.environ.get("NT_RNC", ""))
+        if route == "torch":
+            return rank_loss_torch(sims, dists, self.temp, self.EPS)
+        function = RnCRankLongFunction if route == "long" else RnCRankFunction
+        sims = sims.float().contiguous()
+        return function.apply(sims, dists.detach().float().contiguous(), float(self.temp), self.EPS,
+                              torch.is_grad_enabled() and sims.requires_grad)
 
     def extra_repr(self) -> str:
         return f"(temp): {self.temp:0.1f}"
