@@ -430,7 +430,9 @@ NT_API int nt_softmax_pool(const void* X, const float* scores, const int32_t* se
  *   dX[v]     = alpha[v] dout[g] + ds[v] key[v]   (key = a: Gated; Q[g] / sqrt_key: SDPA)
  *   P[g]      = sum_{v in g} ds[v] X[v]           (ascending v, fp32; Gated: da = sum_g P[g],
  *                                                  db = sum_v ds[v]; SDPA: dQ = P / sqrt_key)
- * alpha is recomputed exactly as nt_softmax_pool computes it.  X, out, dout, a / Q, dX: dtype;
+ * alpha is recomputed exactly as nt_softmax_pool computes it.  With NT_BF16, c_g uses the pooled row
+ * before its rounding to bf16 (summed again from X as nt_softmax_pool does), not the stored out[g]:
+ * sum_v ds[v] is then 0 in every molecule to fp32 rounding.  X, out, dout, a / Q, dX: dtype;
  * scores, ds (n), P (nseg x h), stats (3 nseg workspace): fp32.  node_seg = batch_node_index.
  */
 NT_API int nt_softmax_pool_backward(const void* X, const float* scores, const int32_t* seg_ptr,

@@ -581,7 +581,7 @@ extern "C" int nt_softmax_pool_backward_mixed(const void* X, const float* scores
   const bool vec = h % 8 == 0 && aligned16(X) && aligned16(out) && aligned16(dout) && aligned16(dX) &&
                    aligned16(a ? a : Q);
   // the three launches of nt_softmax_pool_backward; only the per-node kernel reads the key
-  int rc = launch_pool_stats_bf16(vec, scores, seg_ptr, perm, out, dout, nseg, h, stats, stream);
+  int rc = launch_pool_stats_bf16(vec, X, scores, seg_ptr, perm, out, dout, nseg, h, stats, stream);
   if (rc != NT_OK) return rc;
   if (n > 0) {
     rc = vec ? launch_node_backward_mixed<true>(X, scores, node_seg, stats, dout, n, h, a, Q, sqrt_key, dX, ds, stream)

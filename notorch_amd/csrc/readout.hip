@@ -93,13 +93,14 @@ __global__ void __launch_bounds__(256) softmax_pool_kernel(
 //   P[g]     = sum_{v in g} ds_v X[v]                            (Gated: da = sum_g P[g], db = sum_v ds_v;
 //                                                                SDPA: dQ[g] = P[g] / sqrt_key)
 // Three launches: per molecule (m_g, z_g, c_g) on one wave (m and z recomputed exactly as the
-// forward's lanes do, so alpha is bit-identical); per node dX and ds on one wave; P as the forward's
+// forward's lanes do, so alpha is bit-identical; with bf16 rows c_g is taken from the pooled row before
+// its rounding, which the wave sums again from X); per node dX and ds on one wave; P as the forward's
 // pool with the weights ds in place of alpha (ascending node order).
 template <typename T, bool VEC>
 __global__ void __launch_bounds__(256) pool_stats_kernel(
-    const float* __restrict__ s, const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ perm,
-    const T* __restrict__ out, const T* __restrict__ dout, int64_t nseg, int64_t h,
-    float* __restrict__ stats) {
+    const T* __restrict__ X, const float* __restrict__ s, const int32_t* __restrict__ seg_ptr,
+    const int32_t* __restrict__ perm, const T* __restrict__ out, const T* __restrict__ dout, int64_t nseg,
+    int64_t h, float* __restrict__ stats) {
   constexpr int N = Piece<T, VEC>::N;
   const int lane = threadIdx.x & 63;
   const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -113,7 +114,23 @@ __global__ void __launch_bounds__(256) pool_stats_kernel(
     float part = 0.f;
     for (int64_t c = (int64_t)lane * N; c < h; c += 64 * N) {
       float x[N], y[N];
-      Piece<T, VEC>::load(out + g * h + c, x);
+      if constexpr (sizeof(T) == 2) {
+        // bf16 storage: out[g] is the pooled row after its rounding, and c_g taken from it leaves
+        // sum_v ds_v = <dout[g], pooled - out[g]> (2^-9 relative) in place of 0 in every molecule: db, and
+        // a common offset in ds.  The row before the rounding, as softmax_pool_kernel's lane sums it.
+#pragma unroll
+        for (int i = 0; i < N; ++i) x[i] = 0.f;
+        for (int32_t j = b; j < e; ++j) {
+          const int64_t v = perm ? perm[j] : j;
+          const float alpha = expf(s[v] - m) / z;
+          float r[N];
+          Piece<T, VEC>::load(X + v * h + c, r);
+#pragma unroll
+          for (int i = 0; i < N; ++i) x[i] += alpha * r[i];
+        }
+      } else {
+        Piece<T, VEC>::load(out + g * h + c, x);
+      }
       Piece<T, VEC>::load(dout + g * h + c, y);
 #pragma unroll
       for (int i = 0; i < N; ++i) part = fmaf(x[i], y[i], part);
@@ -203,7 +220,7 @@ int launch_pool_backward(const void* X, const float* s, const int32_t* seg_ptr, 
                          void* dX, float* ds, float* P, hipStream_t stream) {
   constexpr int N = Piece<T, VEC>::N;
   pool_stats_kernel<T, VEC><<<grid_for(nseg * 64, 256, 256 * 32), 256, 0, stream>>>(
-      s, seg_ptr, perm, (const T*)out, (const T*)dout, nseg, h, stats);
+      (const T*)X, s, seg_ptr, perm, (const T*)out, (const T*)dout, nseg, h, stats);
   NT_LAUNCH_CHECK();
   if (n > 0) {
     const int grid = grid_for(n * 64, 256, 256 * 32);
@@ -324,10 +341,11 @@ namespace nt {
 namespace {
 
 template <bool VEC>
-int launch_stats_bf16(const float* s, const int32_t* seg_ptr, const int32_t* perm, const void* out,
-                      const void* dout, int64_t nseg, int64_t h, float* stats, hipStream_t stream) {
+int launch_stats_bf16(const void* X, const float* s, const int32_t* seg_ptr, const int32_t* perm,
+                      const void* out, const void* dout, int64_t nseg, int64_t h, float* stats,
+                      hipStream_t stream) {
   pool_stats_kernel<bf16_raw, VEC><<<grid_for(nseg * 64, 256, 256 * 32), 256, 0, stream>>>(
-      s, seg_ptr, perm, (const bf16_raw*)out, (const bf16_raw*)dout, nseg, h, stats);
+      (const bf16_raw*)X, s, seg_ptr, perm, (const bf16_raw*)out, (const bf16_raw*)dout, nseg, h, stats);
   NT_LAUNCH_CHECK();
   return NT_OK;
 }
@@ -344,11 +362,11 @@ int launch_wpool_bf16(const void* X, const float* ds, const int32_t* seg_ptr, co
 
 }  // namespace
 
-int launch_pool_stats_bf16(bool vec, const float* s, const int32_t* seg_ptr, const int32_t* perm,
-                           const void* out, const void* dout, int64_t nseg, int64_t h, float* stats,
-                           hipStream_t stream) {
-  return vec ? launch_stats_bf16<true>(s, seg_ptr, perm, out, dout, nseg, h, stats, stream)
-             : launch_stats_bf16<false>(s, seg_ptr, perm, out, dout, nseg, h, stats, stream);
+int launch_pool_stats_bf16(bool vec, const void* X, const float* s, const int32_t* seg_ptr,
+                           const int32_t* perm, const void* out, const void* dout, int64_t nseg, int64_t h,
+                           float* stats, hipStream_t stream) {
+  return vec ? launch_stats_bf16<true>(X, s, seg_ptr, perm, out, dout, nseg, h, stats, stream)
+             : launch_stats_bf16<false>(X, s, seg_ptr, perm, out, dout, nseg, h, stats, stream);
 }
 
 int launch_weighted_pool_bf16(bool vec, const void* X, const float* ds, const int32_t* seg_ptr,

@@ -120,7 +120,10 @@ class SoftmaxPoolFunction(torch.autograd.Function):
             a=None if sdpa else k, Q=k if sdpa else None, sqrt_key=sqrt_key)
         # ds and P are fp32: an fp32 key (mixed) keeps them unrounded, a bf16 key rounds them once here
         if sdpa:
+            # Q may hold more rows than the batch has molecules (b >= B): the rows past B were never read
             dkey, dbias = (P / sqrt_key).to(key.dtype), None
+            if key.shape[0] > B:
+                dkey = torch.cat([dkey, dkey.new_zeros(key.shape[0] - B, key.shape[1])])
         else:
             dkey = P.sum(0).reshape(key.shape).to(key.dtype)
             dbias = ds.sum().reshape(1).to(key.dtype) if has_bias else None
