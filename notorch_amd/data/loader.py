@@ -78,10 +78,19 @@ class SlotRing:
         self.flags.numpy()[s] = 0
 
     def register(self) -> bool:
-        """Page-lock the ring for DMA (main process, after the workers forked)."""
+        """Page-lock the ring for DMA (main process, after the workers forked).  False where the
+        runtime cannot register host memory it did not allocate (a virtualised device, for one):
+        DevicePrefetcher then copies each batch out of its slot into pinned memory."""
         if not self.registered and torch.cuda.is_available():
             rc = torch.cuda.cudart().cudaHostRegister(self.buf.data_ptr(), self.buf.numel(), 0)
             self.registered = int(rc) == 0
+            if not self.registered:
+                # the runtime keeps the failed call's status for this thread's next launch check to
+                # report: take it.  (The symbol resolves through the library's own dependency, the
+                # HIP runtime torch loaded.)
+                from notorch_amd import _lib
+
+                _lib.load().hipGetLastError()
         return self.registered
 
     def unregister(self) -> None:

@@ -37,9 +37,9 @@ def test_graph_loader_batches_and_forward_bit_identical(pin_threads, ring_slots,
 
 
 def test_graph_feeder_epochs_early_stop_and_shuffle():
-    """graph_loader over the DataLoader-free GraphFeeder (page-locked ring): two epochs, one of them
-    abandoned after two batches, then a shuffled loader; every device batch equals the collate of
-    the same molecules moved with .to(device)."""
+    """graph_loader over the DataLoader-free GraphFeeder (slot ring, page-locked or not: the test
+    below): two epochs, one of them abandoned after two batches, then a shuffled loader; every
+    device batch equals the collate of the same molecules moved with .to(device)."""
     from notorch_amd.data.loader import graph_loader
     from notorch_amd.data.models.graph import BatchedGraph
     from notorch_amd.data.synth import make_batch
@@ -50,7 +50,6 @@ def test_graph_feeder_epochs_early_stop_and_shuffle():
     for stop in (2, None):
         got = []
         for G in loader:
-            assert loader.ring.registered  # page-locked after the workers forked (hipHostRegister)
             got.append(G)
             if stop is not None and len(got) == stop:
                 break
@@ -72,3 +71,27 @@ def test_graph_feeder_epochs_early_stop_and_shuffle():
         for x, y in zip(G.tensors(), ref.tensors()):
             assert torch.equal(x, y)
     shuf.batches.close()
+
+
+def test_feeder_ring_is_page_locked_after_the_workers_forked():
+    """Where the runtime registers host memory it did not allocate, GraphFeeder's ring is page-locked
+    (hipHostRegister) once its workers have forked, and the batches are copied straight out of it."""
+    from notorch_amd.data.loader import SlotRing, graph_loader
+    from notorch_amd.data.models.graph import BatchedGraph
+    from notorch_amd.data.synth import make_batch
+
+    if not SlotRing(1, 1, 4096).register():
+        pytest.skip("hipHostRegister is not supported here")
+    graphs = make_batch("qm9", 128, seed=6).to_graphs()
+    loader = graph_loader(graphs, 64, DEV, num_workers=2, ring_slots=2)
+    got = []
+    for G in loader:
+        assert loader.ring.registered
+        got.append(G)
+    torch.cuda.synchronize()
+    assert len(got) == 2
+    for i, G in enumerate(got):
+        ref = BatchedGraph.from_graphs(graphs[64 * i:64 * (i + 1)]).to(DEV)
+        for x, y in zip(G.tensors(), ref.tensors()):
+            assert torch.equal(x, y)
+    loader.batches.close()
