@@ -151,6 +151,16 @@ def _require_i64(name: str, t: Tensor) -> None:
         raise ValueError(f"{name} must be contiguous")
 
 
+def _require_i32(name: str, t: Tensor, n: int | None = None) -> None:
+    """A contiguous int32 index tensor (CSR pointers, permutations, args) of n entries (if given)."""
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name} must be int32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{name} must have {n} entries, got {t.numel()}")
+
+
 def reduce_code(reduce: str) -> int:
     try:
         return REDUCE_CODES[reduce]
@@ -288,17 +298,20 @@ def segment_reduce(
     out: Tensor | None = None,
 ) -> Tensor:
     """out[s] = reduce over rows X[perm[j]] (j in segment s) of act(row); empty segment -> 0."""
-    dev = _require_device(X, seg_ptr, perm)
+    dev = _require_device(X, seg_ptr, perm, out)
     code = _require_feat("X", X)
-    if out is not None:
-        _require_feat("out", out, X.dtype)
     if X.dim() != 2:
         raise ValueError("X must be 2-D")
-    if seg_ptr.dtype != torch.int32 or seg_ptr.numel() != nseg + 1:
-        raise ValueError("seg_ptr must be int32 of length nseg + 1")
+    _require_i32("seg_ptr", seg_ptr, nseg + 1)
+    if perm is not None:
+        _require_i32("perm", perm, X.shape[0])
     h = X.shape[1]
     if out is None:
         out = torch.empty(nseg, h, dtype=X.dtype, device=dev)
+    else:
+        _require_feat("out", out, X.dtype)
+        if out.shape != (nseg, h):
+            raise ValueError(f"out must be nseg x h = {nseg} x {h}, got {tuple(out.shape)}")
     if X.shape[0] == 0:  # no rows (an edge-free batch): every segment is empty -> 0 (torch_scatter)
         return out.zero_()
     lib = _lib.load()
@@ -389,6 +402,7 @@ def segment_reduce_chunked(
     fp32: amax (1 zero-filled device float, optional) is raised to max|out|."""
     dev = _require_device(X, seg_ptr, perm, amax)
     code = _require_feat("X", X)
+    _require_amax(amax, X.dtype, 1)
     if seg_ptr.dtype != torch.int32 or seg_ptr.numel() != nseg + 1:
         raise ValueError("seg_ptr must be int32 of length nseg + 1")
     cargs = _chunk_args(plan, nseg)
@@ -1104,6 +1118,11 @@ def segment_arg(X: Tensor, seg_ptr: Tensor, perm: Tensor | None, nseg: int, redu
     code = _require_feat("X", X)
     if reduce not in ("max", "min"):
         raise ValueError("segment_arg: reduce must be 'max' or 'min'")
+    if X.dim() != 2:
+        raise ValueError("X must be 2-D")
+    _require_i32("seg_ptr", seg_ptr, nseg + 1)
+    if perm is not None:
+        _require_i32("perm", perm, X.shape[0])
     h = X.shape[1]
     arg = torch.empty(nseg, h, dtype=torch.int32, device=dev)
     if X.shape[0] == 0:  # no rows: every segment is empty
@@ -1122,10 +1141,23 @@ def dmpnn_edge_backward_arg(G: Tensor | None, H: Tensor, dA: Tensor, dS: Tensor,
     code = _require_feat("H", H)
     for n_, t in (("dA", dA), ("dS", dS)) + ((("G", G),) if G is not None else ()):
         _require_feat(n_, t, H.dtype)
-    if amax is not None and code != NT_F32:
-        raise ValueError("amax is fp32 only")
+    _require_amax(amax, H.dtype, 1)
+    if residual and G is None:
+        raise ValueError("residual backward needs G")
+    if H.dim() != 2 or dS.dim() != 2:
+        raise ValueError("H and dS must be 2-D")
     E, h = H.shape
     V = dS.shape[0]
+    if dA.shape != H.shape or dS.shape[1] != h or (G is not None and G.shape != H.shape):
+        raise ValueError("shape mismatch in dmpnn_edge_backward_arg")
+    _require_i32("arg", arg)
+    if arg.shape != dS.shape:
+        raise ValueError(f"arg must be V x h = {V} x {h}, got {tuple(arg.shape)}")
+    _require_i64("dst", dst)
+    if dst.numel() != E:
+        raise ValueError("dst must have one entry per edge")
+    _require_i32("rev_ptr", rev_ptr, E + 1)
+    _require_i32("rev_perm", rev_perm, E)
     out = torch.empty_like(H)
     _run(dev, _lib.load().nt_dmpnn_edge_backward_arg, _ptr(G), _ptr(H), _ptr(dA), _ptr(dS), _ptr(arg),
          _ptr(dst), _ptr(rev_ptr), _ptr(rev_perm), V, E, h, int(residual), act[0], act[1], code,
@@ -1139,11 +1171,18 @@ def gather_rows_arg(X: Tensor, idx: Tensor, arg: Tensor, *, base: Tensor | None 
     dmpnn_edge_backward_arg.  fp32 or bf16."""
     dev = _require_device(X, idx, arg, base, amax)
     code = _require_feat("X", X)
+    _require_amax(amax, X.dtype, 1)
+    if X.dim() != 2:
+        raise ValueError("X must be 2-D")
+    _require_i64("idx", idx)
+    n, h = idx.numel(), X.shape[1]
+    _require_i32("arg", arg)
+    if arg.shape != X.shape:
+        raise ValueError(f"arg must be nseg x h = {X.shape[0]} x {h}, got {tuple(arg.shape)}")
     if base is not None:
         _require_feat("base", base, X.dtype)
-    if amax is not None and code != NT_F32:
-        raise ValueError("amax is fp32 only")
-    n, h = idx.numel(), X.shape[1]
+        if base.shape != (n, h):
+            raise ValueError("base must be n x h")
     out = torch.empty(n, h, dtype=X.dtype, device=dev)
     _run(dev, _lib.load().nt_gather_rows_arg, _ptr(base), _ptr(X), _ptr(idx), _ptr(arg), n, h, code,
          _ptr(out), _ptr(amax), _stream(dev))
@@ -1180,6 +1219,7 @@ def dmpnn_edge_backward(G: Tensor | None, H: Tensor, dA: Tensor, dS: Tensor, dst
     amax (1 zero-filled device float, optional) is raised to max|out|."""
     dev = _require_device(G, H, dA, dS, dst, rev_ptr, rev_perm, dst_ptr, out, amax)
     code = _require_feat("H", H)
+    _require_amax(amax, H.dtype, 1)
     for name, t in (("dA", dA), ("dS", dS)):
         _require_feat(name, t, H.dtype)
     if residual:
@@ -1210,6 +1250,7 @@ def gather_rows(X: Tensor, idx: Tensor, *, base: Tensor | None = None, seg_ptr: 
     when ``seg_ptr`` is given (the backward of a mean scatter); fp32: amax as dmpnn_edge_backward."""
     dev = _require_device(X, idx, base, seg_ptr, out, amax)
     code = _require_feat("X", X)
+    _require_amax(amax, X.dtype, 1)
     _require_i64("idx", idx)
     nseg, h = X.shape
     n = idx.numel()
