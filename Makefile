@@ -36,6 +36,10 @@ $(PYEXT): $(SRC_DIR)/host/collate_py.cpp
 	@mkdir -p $(dir $@)
 	g++ -O3 -std=c++17 -shared -fPIC -Wall $(TORCH_FLAGS) $< -o $@ -ltorch_python -ltorch_cpu -lc10
 
+# pairwise.hip is plain fp32 VALU code: built without the packed fp32 instructions (v_pk_*_f32), so its
+# sums are the scalar instructions' in the order the source gives
+$(BDIR)/pairwise.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+
 $(BDIR)/%.o: $(SRC_DIR)/%.hip $(HDRS)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(FLAGS) -c $< -o $@

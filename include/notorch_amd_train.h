@@ -275,6 +275,41 @@ NT_API int64_t nt_rank_metric_long_workspace(int64_t n, int64_t t);
 NT_API int nt_rank_metric_long(const float* scores, const float* targets, const uint8_t* mask, int64_t n,
                                int64_t t, float* out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * Pairwise p-norm of rows, p in {1, 2}, in the direct difference form, and its gradient (csrc/pairwise.hip;
+ * additive to ABI 8): what nn/loss/rnc.py's PNorm computes, the two inputs of RankNContrastLoss.
+ *   X[i,j] = s (sum_k |a_i[k] - b_j[k]|^p)^(1/p),   s = -1 when negate, else 1
+ * A: n x d, B: m x d, contiguous, both of `dtype` (NT_F32, or NT_BF16 widened exactly as loaded); X: n x m
+ * fp32.  B == NULL means B = A (m must equal n): only the 128 x 128 tiles on and above the diagonal are
+ * computed and each is also written transposed, so X is bitwise symmetric; its diagonal is exactly 0, as is
+ * every pair of equal rows in any mode.  Any d (the kernel walks k in chunks of 16; d = 0 gives zeros); n m is
+ * indexed in 64 bits.  Per element the error is within (d + 4) 2^-24 |X| (a sum of d non-negative terms).
+ * Rows are loaded as whole pieces of 4 elements when d % 4 == 0 and A and B are aligned to a piece (16 bytes
+ * fp32, 8 bytes bf16), else by element; X leaves as 16-byte pieces when m % 4 == 0 and X is 16-byte aligned.
+ *
+ *   dA[i,k] = sum_j w_ij phi(a_i[k] - b_j[k])       (nt_pairwise_pnorm_backward; dA: n x d fp32)
+ *   p = 1: phi = sign with sign(0) = 0, w = g;   p = 2: phi(t) = t, w = g / |X|, 0 where X == 0
+ * (torch's convention for the direct form: equal rows contribute a finite 0).  g_ij = G[i,j] (use_g; G and X
+ * are n x m), or G[j,i] (use_gt; G and X are m x n), or their sum (both; n == m); X is read at the indices of
+ * G and only with p = 2; negate flips the sign.  dA of X = f(A, B): (A, B, use_g); dB: (B, A, use_gt) with
+ * n and m exchanged; B = A: (A, A, both flags), one pass.  B is required here.
+ * j is summed in ascending chunks of 32 without atomics.  When the shape has fewer than 256 (row, k) tiles,
+ * j is split over workgroups whose partial sums go to `workspace` and are added in split order by a second
+ * launch: nt_pairwise_pnorm_backward_workspace(n, m, d) bytes (0 when one launch does it; -1 for bad sizes)
+ * of caller-owned device memory, 16-byte aligned.  The plan depends on the shape alone: two calls return the
+ * same bits, forward and backward.  Stream-ordered; nothing is allocated or read back.
+ * Checked on the host before any device call: p outside {1, 2} or another dtype (NT_EUNSUPPORTED); a NULL
+ * pointer, negative sizes or sizes beyond 2^40 elements, B == NULL with m != n, neither flag, both flags with
+ * m != n, a missing, misaligned or short workspace (NT_EINVAL).  n == 0 or m == 0 returns at once (the
+ * backward then writes nothing: the empty sum is the caller's zero-fill), as does the backward with d == 0.
+ */
+NT_API int nt_pairwise_pnorm(const void* A, const void* B, int64_t n, int64_t m, int64_t d, int dtype, int p,
+                             int negate, float* X, void* stream);
+NT_API int64_t nt_pairwise_pnorm_backward_workspace(int64_t n, int64_t m, int64_t d);
+NT_API int nt_pairwise_pnorm_backward(const void* A, const void* B, const float* X, const float* G, int64_t n,
+                                      int64_t m, int64_t d, int dtype, int p, int negate, int use_g, int use_gt,
+                                      float* dA, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -202,6 +202,14 @@ EXT_SIGNATURES: dict[str, tuple] = {
     "nt_rank_metric_long_max_n": (_c_i64, []),
     "nt_rank_metric_long_workspace": (_c_i64, [_c_i64, _c_i64]),
     "nt_rank_metric_long": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp]),
+    # pairwise p-norm, p in {1, 2} (csrc/pairwise.hip): A, B | NULL, n, m, d, dtype, p, negate, X
+    "nt_pairwise_pnorm": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp]),
+    # its gradient: A, B, X, G, n, m, d, dtype, p, negate, use_g, use_gt, dA, workspace, workspace_bytes
+    "nt_pairwise_pnorm_backward_workspace": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "nt_pairwise_pnorm_backward": (
+        _c_int,
+        [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, _vp],
+    ),
 }
 
 # kind codes of nt_task_loss (include/notorch_amd_train.h)

@@ -55,6 +55,8 @@ __all__ = [
     "rnc_rank",
     "rnc_long_max_n",
     "rnc_rank_long",
+    "pairwise_pnorm",
+    "pairwise_pnorm_backward",
     "task_loss",
     "task_loss_single_max",
     "rank_metric",
@@ -1655,6 +1657,66 @@ def rnc_rank_long(sim: Tensor, dist: Tensor, temp: float, eps: float,
     """rnc_rank for n up to rnc_long_max_n() (nt_rnc_rank_long): the same arguments and results, equal to
     rnc_rank's to fp32 rounding (the per-thread part of the sums has another, equally fixed, order)."""
     return _rnc_rank("nt_rnc_rank_long", sim, dist, temp, eps, need_grad)
+
+
+# ------------------------------------------------------------------------- pairwise p-norm (PNorm)
+def _require_pairwise(A: Tensor, B: Tensor | None, p) -> tuple[torch.device, int]:
+    dev = _require_device(A, B)
+    code = _require_feat("A", A)
+    if A.dim() != 2:
+        raise ValueError(f"A must be n x d, got {tuple(A.shape)}")
+    if B is not None:
+        _require_feat("B", B, A.dtype)
+        if B.dim() != 2 or B.shape[1] != A.shape[1]:
+            raise ValueError(f"B must be m x {A.shape[1]} like A, got {tuple(B.shape)}")
+    if p not in (1, 2):
+        raise ValueError(f"the pairwise kernels take p = 1 or p = 2, got {p}")
+    return dev, code
+
+
+def pairwise_pnorm(A: Tensor, B: Tensor | None = None, *, p, negate: bool = False) -> Tensor:
+    """X[i, j] = (sum_k |A[i, k] - B[j, k]|^p)^(1/p), negated with ``negate`` (nt_pairwise_pnorm): A n x d and B
+    m x d, both fp32 or both bf16 (widened exactly), X n x m fp32 in the direct difference form.  B = None is
+    B = A: X is then bitwise symmetric with a diagonal of exact zeros."""
+    dev, code = _require_pairwise(A, B, p)
+    n, d = A.shape
+    m = n if B is None else B.shape[0]
+    X = torch.empty(n, m, dtype=torch.float32, device=dev)
+    _run(dev, _lib.load().nt_pairwise_pnorm, _ptr(A), _ptr(B), n, m, d, code, int(p), int(bool(negate)), _ptr(X),
+         _stream(dev))
+    return X
+
+
+def pairwise_pnorm_backward(A: Tensor, B: Tensor | None, X: Tensor, G: Tensor, *, p, negate: bool = False,
+                            want: tuple = ("A",)) -> tuple[Tensor | None, Tensor | None]:
+    """The gradients of X = pairwise_pnorm(A, B) for dL/dX = G (nt_pairwise_pnorm_backward): (dA, dB) in fp32,
+    None where ``want`` does not name it.  B = None is B = A: dA then holds both uses of A, from one pass that
+    reads G[i, j] + G[j, i].  X and G are contiguous fp32 n x m."""
+    dev, code = _require_pairwise(A, B, p)
+    _require_device(X, G)
+    n, d = A.shape
+    m = n if B is None else B.shape[0]
+    for name, t in (("X", X), ("G", G)):
+        _require_f32(name, t)
+        if tuple(t.shape) != (n, m):
+            raise ValueError(f"{name} must be {n} x {m}, got {tuple(t.shape)}")
+    if not set(want) <= {"A", "B"} or (B is None and "B" in want):
+        raise ValueError(f"want names 'A' and / or 'B' (no 'B' without a B), got {want!r}")
+    lib = _lib.load()
+
+    def run(P: Tensor, Q: Tensor, use_g: bool, use_gt: bool) -> Tensor:
+        rows, cols = P.shape[0], Q.shape[0]
+        out = torch.empty(rows, d, dtype=torch.float32, device=dev) if cols else \
+            torch.zeros(rows, d, dtype=torch.float32, device=dev)
+        ws_bytes = int(lib.nt_pairwise_pnorm_backward_workspace(rows, cols, d))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+        _run(dev, lib.nt_pairwise_pnorm_backward, _ptr(P), _ptr(Q), _ptr(X), _ptr(G), rows, cols, d, code, int(p),
+             int(bool(negate)), int(use_g), int(use_gt), _ptr(out), _ptr(ws), ws_bytes, _stream(dev))
+        return out
+
+    if B is None:
+        return (run(A, A, True, True) if "A" in want else None), None
+    return (run(A, B, True, False) if "A" in want else None), (run(B, A, False, True) if "B" in want else None)
 
 
 # ------------------------------------------------------------------------- task losses and ranking metrics

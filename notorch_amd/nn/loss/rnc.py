@@ -21,6 +21,11 @@ Three routes, chosen by ``rnc_route`` without a device-to-host copy (``N`` comes
 
 ``NT_RNC`` is read from the environment per call.
 
+``PNorm`` (the default distance, p = 1, and similarity, p = 2 negated) is ``torch.cdist``, or for 2-D fp32 /
+bf16 ROCm tensors the direct-form HIP kernels ``nt_pairwise_pnorm`` / ``nt_pairwise_pnorm_backward``
+(``PairwisePNormFunction``): for the p in ``PNORM_KERNEL_P``, or for p = 1 and 2 with ``NT_PNORM=kernel``;
+``NT_PNORM=torch`` never takes them (``pnorm_route``; read per call).
+
 ``k = i`` is inside the sum exactly when ``D[i,j] <= D[i,i]`` (duplicated targets), as in the reference.
 One deliberate difference: the loss is evaluated as ``log denom - Sim / temp``, which stays finite where
 the reference's ``log(s / denom)`` returns ``inf`` because ``s`` underflowed.  Non-finite entries of
@@ -38,7 +43,7 @@ from torch import Tensor
 from notorch_amd import kernels as K
 
 __all__ = ["RankNContrastLoss", "CDist", "PNorm", "RnCRankFunction", "RnCRankLongFunction", "rnc_route",
-           "RNC_LONG_DEFAULT_MAX_N"]
+           "RNC_LONG_DEFAULT_MAX_N", "PairwisePNormFunction", "pnorm_route", "PNORM_KERNEL_P"]
 
 # Largest N that takes nt_rnc_rank_long without NT_RNC=kernel: the largest N timed by tools/rnc_bench.py at
 # which, as at every smaller timed N, the kernel's median is below the torch route's by more than the torch
@@ -61,6 +66,45 @@ class CDist(nn.Module):
 _CDIST_PAIRS = 1 << 23
 
 
+# The p that take the pairwise kernels (csrc/pairwise.hip) without NT_PNORM=kernel: a p is listed only if, at
+# every shape tools/pnorm_bench.py times for it, the kernel's median is below the torch.cdist route's by more
+# than that route's spread, forward and forward + backward (DESIGN.md §4 has the table).
+PNORM_KERNEL_P: tuple = ()
+
+
+class PairwisePNormFunction(torch.autograd.Function):
+    """``K.pairwise_pnorm`` with ``K.pairwise_pnorm_backward`` as its gradient.  ``B = None`` is ``B = A`` (one
+    backward pass gives A both of its uses).  X is fp32; each gradient comes back in its input's dtype."""
+
+    @staticmethod
+    def forward(ctx, A: Tensor, B: Tensor | None, p: int, negate: bool) -> Tensor:
+        X = K.pairwise_pnorm(A, B, p=p, negate=negate)
+        ctx.p, ctx.negate = p, negate
+        ctx.save_for_backward(A, B, X)  # kept only when a gradient is recorded
+        return X
+
+    @staticmethod
+    def backward(ctx, G: Tensor):
+        A, B, X = ctx.saved_tensors
+        want = tuple(name for name, t, need in (("A", A, ctx.needs_input_grad[0]), ("B", B, ctx.needs_input_grad[1]))
+                     if t is not None and need)
+        dA, dB = K.pairwise_pnorm_backward(A, B, X, G.float().contiguous(), p=ctx.p, negate=ctx.negate, want=want)
+        return (None if dA is None else dA.to(A.dtype)), (None if dB is None else dB.to(B.dtype)), None, None
+
+
+def pnorm_route(p: float, device_type: str, dtype_a: torch.dtype, dtype_b: torch.dtype, dims_ok: bool,
+                knob: str) -> str:
+    """Which route a PNorm call takes: ``"kernel"`` (``PairwisePNormFunction``) or ``"torch"`` (``torch.cdist``).
+    ``dims_ok``: both operands 2-D with the same number of columns.  ``knob`` is the value of ``NT_PNORM``:
+    ``"torch"`` never takes the kernel, ``"kernel"`` takes it for p = 1 and p = 2 whatever ``PNORM_KERNEL_P``
+    lists."""
+    if device_type != "cuda" or not dims_ok or dtype_a != dtype_b or dtype_a not in (torch.float32, torch.bfloat16):
+        return "torch"
+    if knob == "torch" or p not in (1, 2):
+        return "torch"
+    return "kernel" if knob == "kernel" or p in PNORM_KERNEL_P else "torch"
+
+
 class PNorm(CDist):
     def __init__(self, p: float = 2.0, negate: bool = False) -> None:
         super().__init__()
@@ -69,7 +113,15 @@ class PNorm(CDist):
         self.negate = negate
 
     def forward(self, A: Tensor, B: Tensor | None = None) -> Tensor:
-        B = A if B is None else B
+        other = A if B is None else B
+        dims_ok = A.dim() == 2 and other.dim() == 2 and A.shape[1] == other.shape[1]
+        device = "cuda" if A.is_cuda and other.is_cuda else "cpu"
+        if pnorm_route(self.p, device, A.dtype, other.dtype, dims_ok, os.environ.get("NT_PNORM", "")) == "kernel":
+            X = PairwisePNormFunction.apply(A.contiguous(), None if other is A else other.contiguous(),
+                                            int(self.p), self.negate)
+            # torch.cdist answers bf16 operands in bf16, and in fp32 under autocast
+            return X if A.dtype == torch.float32 or torch.is_autocast_enabled() else X.to(A.dtype)
+        B = other
         rows = max(1, _CDIST_PAIRS // max(1, B.shape[-2]))
         if self.p != 2 and A.is_cuda and A.dim() == 2 and A.shape[0] > rows:
             X = torch.cat([torch.cdist(a, B, p=self.p) for a in A.split(rows)])
