@@ -310,6 +310,37 @@ NT_API int nt_pairwise_pnorm_backward(const void* A, const void* B, const float*
                                       int64_t m, int64_t d, int dtype, int p, int negate, int use_g, int use_gt,
                                       float* dA, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * The Dirichlet loss of notorch/nn/loss/loss.py (Sensoy et al., NeurIPS 2018), its masked weighted reduction
+ * and the gradient of the reduced loss (csrc/dirichlet_loss.hip, csrc/dirichlet_math.hpp; additive to ABI 8).
+ *
+ * preds: b x t x k logits, contiguous, preds_dtype NT_F32 or NT_BF16 (widened as loaded); targets: b x t fp32,
+ * the true class (int)y; mask: b x t bytes or NULL; sample_weights: b fp32 or NULL.  Per element, in fp32:
+ *   a_c = softplus(x_c) + 1,  S = sum a_c,  p_c = a_c / S,  q = sum p_c^2,  St = S - a_y + 1
+ *   L = (1 - 2 p_y + q) + (1 - q) / (S + 1)
+ *       + v_kl (lgamma(St) - sum_{c != y} lgamma(a_c) - lgamma(k) + sum_{c != y} (a_c - 1) (psi(a_c) - psi(St)))
+ * with the KL term evaluated in a form that does not cancel at large a (dirichlet_math.hpp): per element loss
+ * and gradient stay within 1e-5 of fp64 on the scales max(1, |L|) and max(1, max_c |g_c|) up to logits of 1e4.
+ * A target that is no class (y < 0, y >= k, NaN) makes the element's loss and its k gradients NaN, as
+ * NT_LOSS_XENT does.  loss[0] and dpreds are reduced and scaled as nt_task_loss's: w[i] m[i,j] / den, an
+ * all-false mask gives NaN, dpreds (preds_dtype, rounded to nearest even; NULL: loss only) is for a unit
+ * upstream gradient.
+ *
+ * An element is evaluated by W consecutive lanes, W the smallest power of two >= k and at most 64, a class (or,
+ * above 64, every W-th class) per lane.  b t W <= 8192 lane slots: ONE launch of one workgroup, no workspace.
+ * Above: a partial launch (one workgroup per 8192 slots), a finalize and, with dpreds, a gradient launch, as
+ * in nt_task_loss.  Every sum runs in an order fixed by (b, t, k); no float atomics; two calls return the same
+ * bits.  Nothing is read back.  workspace: nt_dirichlet_loss_workspace(b, t, k) bytes (0 in the one-launch case:
+ * NULL is accepted then; -1 for bad sizes) of caller-owned device memory, 16-byte aligned.
+ * Checked on the host before any device call: NULL preds / targets / loss (NT_EINVAL); a preds_dtype other than
+ * NT_F32 / NT_BF16 (NT_EUNSUPPORTED); b, t < 0, k < 1 or more than 2^40 logits, a short, missing or misaligned
+ * workspace (NT_EINVAL).  b t == 0 launches nothing (loss is not written).
+ */
+NT_API int64_t nt_dirichlet_loss_workspace(int64_t b, int64_t t, int64_t k);
+NT_API int nt_dirichlet_loss(const void* preds, int preds_dtype, const float* targets, const uint8_t* mask,
+                             const float* sample_weights, int64_t b, int64_t t, int64_t k, float v_kl, float* loss,
+                             void* dpreds, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,12 @@ EXT_SIGNATURES: dict[str, tuple] = {
         _c_int,
         [_vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, _vp],
     ),
+    # the Dirichlet loss (csrc/dirichlet_loss.hip): preds, preds_dtype, targets, mask, sample_weights, b, t, k,
+    # v_kl, loss, dpreds | NULL, workspace, workspace_bytes
+    "nt_dirichlet_loss_workspace": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "nt_dirichlet_loss": (
+        _c_int, [_vp, _c_int, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_f32, _vp, _vp, _vp, _c_i64, _vp],
+    ),
 }
 
 # kind codes of nt_task_loss (include/notorch_amd_train.h)

@@ -59,6 +59,7 @@ __all__ = [
     "pairwise_pnorm_backward",
     "task_loss",
     "task_loss_single_max",
+    "dirichlet_loss",
     "rank_metric",
     "rank_metric_long",
     "rank_metric_long_max_n",
@@ -1769,6 +1770,36 @@ def task_loss(preds: Tensor, targets: Tensor, kind: str, mask: Tensor | None = N
          _ptr(preds), code, _ptr(targets), _ptr(masks[0]), _ptr(sample_weights), _ptr(masks[1]), _ptr(masks[2]),
          b, t, c, _lib.LOSS_CODES[kind], float(v_kl), float(eps), _ptr(loss), _ptr(dpreds), _ptr(ws), ws_bytes,
          _stream(dev))
+    return loss, dpreds
+
+
+def dirichlet_loss(preds: Tensor, targets: Tensor, mask: Tensor | None = None,
+                   sample_weights: Tensor | None = None, v_kl: float = 0.2,
+                   need_grad: bool = False) -> tuple[Tensor, Tensor | None]:
+    """The Dirichlet loss of b x t x k logits (fp32 or bf16) against b x t fp32 class indices, its masked weighted
+    reduction and, with need_grad, dLoss/dpreds from the same call (nt_dirichlet_loss, class-parallel: one launch
+    while b t W <= 8192, W the power of two >= k up to 64).  mask b x t bool, sample_weights b fp32.  Returns
+    (loss, a 0-d fp32 tensor; dpreds in the dtype of preds, or None: no gradient buffer is allocated)."""
+    dev = _require_device(preds, targets, mask, sample_weights)
+    code = _require_feat("preds", preds)
+    _require_f32("targets", targets)
+    if targets.dim() != 2 or preds.dim() != 3 or tuple(preds.shape[:2]) != tuple(targets.shape) or preds.shape[2] < 1:
+        raise ValueError(f"preds must be b x t x k (k >= 1) and targets b x t, got {tuple(preds.shape)} and "
+                         f"{tuple(targets.shape)}")
+    b, t, k = preds.shape
+    m = _byte_mask("mask", mask, (b, t))
+    if sample_weights is not None:
+        _require_f32("sample_weights", sample_weights)
+        if tuple(sample_weights.shape) != (b,):
+            raise ValueError(f"sample_weights must have shape ({b},), got {tuple(sample_weights.shape)}")
+    lib = _lib.load()
+    loss = torch.full((), float("nan"), dtype=torch.float32, device=dev) if b * t == 0 else \
+        torch.empty((), dtype=torch.float32, device=dev)
+    dpreds = torch.empty_like(preds) if need_grad else None
+    ws_bytes = int(lib.nt_dirichlet_loss_workspace(b, t, k))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    _run(dev, lib.nt_dirichlet_loss, _ptr(preds), code, _ptr(targets), _ptr(m), _ptr(sample_weights), b, t, k,
+         float(v_kl), _ptr(loss), _ptr(dpreds), _ptr(ws), ws_bytes, _stream(dev))
     return loss, dpreds
 
 

@@ -20,7 +20,9 @@ Two routes, chosen from devices, dtypes and ``requires_grad`` alone (nothing is 
 ``NT_LOSS`` in the environment, read per call, overrides the choice on device tensors: ``torch`` forces
 torch ops, ``kernel`` forces the kernel.  Without it a kind takes the kernel unless it is listed in
 ``TORCH_BY_DEFAULT`` (the kinds whose training step measured slower on the kernel: DESIGN.md section 4).
-``Dirichlet`` is torch ops only (its gradient needs a trigamma).
+``Dirichlet`` has a kernel of its own, ``nt_dirichlet_loss`` through :class:`DirichletLossFunction` (class-parallel:
+its k classes are spread over lanes), under the same conditions and the same knob; its name in ``TORCH_BY_DEFAULT``
+is ``"dirichlet"``.  ``KIND`` stays ``None``: it is not one of ``nt_task_loss``'s element losses.
 """
 from __future__ import annotations
 
@@ -48,6 +50,7 @@ __all__ = [
     "XENT",
     "Dirichlet",
     "TaskLossFunction",
+    "DirichletLossFunction",
 ]
 
 # kinds that take torch ops on device tensors unless NT_LOSS=kernel (see the module docstring)
@@ -84,6 +87,22 @@ class TaskLossFunction(torch.autograd.Function):
         return (dpreds * grad_out.to(dpreds.dtype),) + (None,) * 9
 
 
+class DirichletLossFunction(torch.autograd.Function):
+    """:class:`TaskLossFunction` for the Dirichlet loss: ``nt_dirichlet_loss`` returns the loss and, with
+    ``need_grad``, ``dLoss/dalphas`` for a unit upstream gradient; backward is one multiply."""
+
+    @staticmethod
+    def forward(ctx, alphas, targets, mask, sample_weights, v_kl, need_grad):
+        loss, dalphas = K.dirichlet_loss(alphas, targets, mask, sample_weights, v_kl, need_grad)
+        ctx.save_for_backward(dalphas)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dalphas,) = ctx.saved_tensors
+        return (dalphas * grad_out.to(dalphas.dtype),) + (None,) * 5
+
+
 def _as_bool(m: Tensor | None) -> Tensor | None:
     if m is None or m.dtype == torch.bool:
         return m
@@ -118,7 +137,12 @@ class _LossFunctionBase(nn.Module):
         return self._reduce(self._element(preds, targets), mask, sample_weights)
 
     def _kernel_route(self, preds, targets, mask=None, sample_weights=None, lt_mask=None, gt_mask=None) -> bool:
-        if self.KIND is None or not preds.is_cuda or preds.dtype not in (torch.float32, torch.bfloat16):
+        return self.KIND is not None and self._device_route(self.KIND, preds, targets, mask, sample_weights, lt_mask,
+                                                            gt_mask)
+
+    @staticmethod
+    def _device_route(name, preds, targets, mask=None, sample_weights=None, lt_mask=None, gt_mask=None) -> bool:
+        if not preds.is_cuda or preds.dtype not in (torch.float32, torch.bfloat16):
             return False
         others = (targets, mask, sample_weights, lt_mask, gt_mask)
         if any(x is not None and x.device != preds.device for x in others):
@@ -131,7 +155,7 @@ class _LossFunctionBase(nn.Module):
         knob = os.environ.get("NT_LOSS", "")
         if knob in ("torch", "kernel"):
             return knob == "kernel"
-        return self.KIND not in TORCH_BY_DEFAULT
+        return name not in TORCH_BY_DEFAULT
 
     def _reduce(self, loss: Tensor, mask: Tensor | None = None, sample_weights: Tensor | None = None) -> Tensor:
         if not loss.is_floating_point():
@@ -217,7 +241,8 @@ class CrossEntropy(_LossFunctionBase):
 
 class Dirichlet(_LossFunctionBase):
     """The loss of Sensoy et al., "Evidential deep learning to quantify classification uncertainty", NeurIPS
-    2018, for ``alphas.shape[-1]`` classes (the reference hard-codes two).  Torch ops on every device."""
+    2018, for ``alphas.shape[-1]`` classes (the reference hard-codes two).  Device fp32 / bf16 ``alphas`` (b x t x k)
+    take ``nt_dirichlet_loss``; there a target that is no class gives a NaN element where ``one_hot`` raises."""
 
     def __init__(self, v_kl: float = 0.2) -> None:
         super().__init__()
@@ -225,6 +250,11 @@ class Dirichlet(_LossFunctionBase):
         self.v_kl = v_kl
 
     def forward(self, alphas, targets, *, mask=None, sample_weights=None, **kwargs):
+        if alphas.dim() == 3 and alphas.shape[2] >= 1 and self._device_route("dirichlet", alphas, targets, mask, sample_weights):
+            sw = None if sample_weights is None else sample_weights.detach().float().contiguous()
+            mk = None if mask is None else _as_bool(mask).contiguous()
+            return DirichletLossFunction.apply(alphas.contiguous(), targets.detach().float().contiguous(), mk, sw,
+                                               float(self.v_kl), torch.is_grad_enabled() and alphas.requires_grad)
         return self._forward(alphas, targets, mask, sample_weights)
 
     def _element(self, alphas, targets):

@@ -30,12 +30,14 @@ nn.Linear(h, tasks * c) on the readout (c = 1, 2, 4; softplus on the variance-li
 alpha + 1, beta + 0.1), then notorch_amd.nn.loss.MSE / MVE / Evidential against fixed randn targets.  The head
 is in the optimizer.  The loss takes the kernel (nt_task_loss, one launch for loss and gradient) or, with
 NT_LOSS=torch in the environment, torch ops under autograd; the JSON names the route.
+--loss dirichlet: the head's tasks * 2 raw logits go to notorch_amd.nn.loss.Dirichlet against fixed 0 / 1 classes
+(nt_dirichlet_loss, or the torch-ops chain with NT_LOSS=torch).
 The table and the JSON also report torch.cuda.max_memory_allocated over the timed steps.
 Usage: python tools/train_bench.py [--kind qm9] [--mols 4096] [--h 300] [--depth 3] [--dtype f32|bf16]
                                   [--steps 30] [--warmup 10] [--warmup-s 0] [--modes kernel,torch]
                                   [--optim adam|none] [--embedded [--embed-bwd kernel|torch]] [--autocast]
                                   [--dropout P] [--readout sum|gated|gated-f32]
-                                  [--loss mse|mve|evidential [--tasks 1]] [--json]"""
+                                  [--loss mse|mve|evidential|dirichlet [--tasks 1]] [--json]"""
 import argparse
 import contextlib
 import json
@@ -84,7 +86,7 @@ def main():
                    help="sum: the Sum readout; gated: a trained Gated readout on the block's output as it is "
                         "(under --autocast: bf16 rows, fp32 keys, inside the region); gated-f32: the same readout "
                         "on node_feats.float(), outside the autocast region")
-    p.add_argument("--loss", default=None, choices=["mse", "mve", "evidential"],
+    p.add_argument("--loss", default=None, choices=["mse", "mve", "evidential", "dirichlet"],
                    help="close the step with an nn.Linear(h, tasks * c) head and this loss (NT_LOSS=torch: the torch-ops "
                         "route) in place of out.pow(2).sum()")
     p.add_argument("--tasks", type=int, default=1, help="with --loss: the number of target columns t")
@@ -121,10 +123,13 @@ def main():
     if a.loss:
         from notorch_amd.nn import loss as losses
 
-        c = {"mse": 1, "mve": 2, "evidential": 4}[a.loss]
+        c = {"mse": 1, "mve": 2, "evidential": 4, "dirichlet": 2}[a.loss]
         head = torch.nn.Linear(a.h, a.tasks * c).to("cuda", dt).train()
-        crit = {"mse": losses.MSE, "mve": losses.MVE, "evidential": losses.Evidential}[a.loss]()
+        crit = {"mse": losses.MSE, "mve": losses.MVE, "evidential": losses.Evidential,
+                "dirichlet": losses.Dirichlet}[a.loss]()
         targets = torch.randn(a.mols, a.tasks, device="cuda")
+        if a.loss == "dirichlet":
+            targets = (targets > 0).float()
         shift = torch.tensor([0.0, 0.1, 1.0, 0.1][:c], device="cuda")[1:]
 
     def task_loss(x):
@@ -133,6 +138,8 @@ def main():
         out = head(x).view(a.mols, a.tasks, -1)
         if out.shape[-1] == 1:
             return crit(out.squeeze(-1), targets)
+        if a.loss == "dirichlet":
+            return crit(out, targets)
         wide = torch.nn.functional.softplus(out[..., 1:]) + shift.to(out.dtype)
         return crit(torch.cat([out[..., :1], wide], -1), targets)
 
@@ -215,7 +222,8 @@ def main():
             **({"autocast": "bf16"} if a.autocast else {}),
             **({"readout": a.readout} if a.readout != "sum" else {}),
             **({"loss": a.loss, "tasks": a.tasks,
-                "loss_route": "kernel" if crit._kernel_route(torch.empty(1, 1, device="cuda", dtype=dt),
+                "loss_route": "kernel" if crit._device_route("dirichlet" if a.loss == "dirichlet" else crit.KIND,
+                                                             torch.empty(1, 1, device="cuda", dtype=dt),
                                                              targets[:1, :1]) else "torch"} if a.loss else {}),
             **layer,
             "max_memory_allocated": mem,
