@@ -50,7 +50,7 @@ $(OUT): $(OBJS)
 
 # resource usage report (VGPR / SGPR / LDS / occupancy) of every kernel
 resource-usage: $(SRCS)
-	@for f in $(SRCS); do $(HIPCC) $(FLAGS) -c $$f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs|LDS Size|Occupancy|SGPRs:"; done
+	@for f in $(SRCS); do $(HIPCC) $(FLAGS) -c $$f -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|AGPRs|ScratchSize|LDS Size|Occupancy|SGPRs:"; done
 
 clean:
 	rm -rf build notorch_amd/lib/libnotorch_amd.so $(PYEXT)

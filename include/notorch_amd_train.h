@@ -341,6 +341,34 @@ NT_API int nt_dirichlet_loss(const void* preds, int preds_dtype, const float* ta
                              const float* sample_weights, int64_t b, int64_t t, int64_t k, float v_kl, float* loss,
                              void* dpreds, void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * The MLP predictor head of nn/mlp.py in one launch (csrc/mlp_head.hip; additive to ABI 8), inference forward:
+ *   y = L_n(act(... act(L_1(x)) ...)),   L_i(v) = v W_i^T + b_i,   1 <= nlayers <= 8
+ * x: rows x dims[0], unit column stride, rows x_pitch elements apart; W[i]: dims[i+1] x dims[i] contiguous
+ * (nn.Linear's layout, no packing); b[i]: dims[i+1] or NULL (b itself may be NULL: no biases); out: rows x
+ * dims[nlayers] contiguous.  W and b are host arrays of nlayers device pointers, read during the call only: the
+ * layer descriptors travel by value in the kernel arguments.  act is one NT_ACT_* code for the whole chain.
+ * A workgroup keeps 16 rows' activations in two LDS tiles through every layer; hidden activations never reach
+ * global memory.  out_dtype selects the instance:
+ *   NT_F32   fp32 x and fp32 parameters, v_mfma_f32_16x16x4_f32: the exact fp32 fma chain
+ *   NT_BF16  x and the parameters NT_F32 or NT_BF16 each, fp32 rounded to bf16 as loaded (biases too),
+ *            v_mfma_f32_16x16x32_bf16 with fp32 accumulation; a layer's output is rounded to bf16 after the bias
+ *            and again after the activation: what nn.Linear and the activation give under bf16 autocast
+ * nt_mlp_head_supported (1 / 0) states the limits once: dtypes NT_F32 / NT_BF16, 1 <= nlayers <= 8,
+ * 1 <= dims[0] <= 8192 (read from global memory), 1 <= dims[i] <= 1264 for i >= 1 (two 16-row fp32 tiles of
+ * 64-byte k steps plus 32 bytes of padding per row fill the 160 KiB of LDS at 1264; 1265 does not fit).
+ * Rows, k and column tails are predicated in the kernel; rows that are not 16-byte aligned load by element.
+ * Checked on the host before any device call: NULL x / W / W[i] / dims / out, nlayers outside 1..8, rows < 0 or a
+ * dims entry < 1, an act code outside NT_ACT_*, x_pitch < dims[0], a padded x_pitch (> dims[0]) that is no
+ * multiple of 16 bytes (NT_EINVAL); another dtype, an fp32 out with a bf16 operand, widths beyond the limits
+ * (NT_EUNSUPPORTED).  rows == 0 returns NT_OK without a launch.  nt_last_kernel reports "mlp_head_f32" or
+ * "mlp_head_bf16".  Stream-ordered; nothing is allocated or read back.
+ */
+NT_API int nt_mlp_head_supported(int x_dtype, int param_dtype, int nlayers, const int64_t* dims);
+NT_API int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
+                               const void* const* W, const void* const* b, int param_dtype, const int64_t* dims,
+                               int act, float act_alpha, void* out, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -216,6 +216,12 @@ EXT_SIGNATURES: dict[str, tuple] = {
     "nt_dirichlet_loss": (
         _c_int, [_vp, _c_int, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_f32, _vp, _vp, _vp, _c_i64, _vp],
     ),
+    # the fused MLP head (csrc/mlp_head.hip): x_dtype, param_dtype, nlayers, dims[nlayers + 1]
+    "nt_mlp_head_supported": (_c_int, [_c_int, _c_int, _c_int, _vp]),
+    # x, x_dtype, rows, x_pitch, nlayers, W[nlayers], b[nlayers] | NULL, param_dtype, dims, act, alpha, out, out_dtype
+    "nt_mlp_head_forward": (
+        _c_int, [_vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_f32, _vp, _c_int, _vp],
+    ),
 }
 
 # kind codes of nt_task_loss (include/notorch_amd_train.h)

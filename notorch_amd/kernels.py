@@ -64,6 +64,8 @@ __all__ = [
     "rank_metric_long",
     "rank_metric_long_max_n",
     "rank_metric_max_n",
+    "mlp_head_supported",
+    "mlp_head",
 ]
 
 
@@ -1852,3 +1854,67 @@ def rank_metric_long(scores: Tensor, targets: Tensor, mask: Tensor | None = None
     _run(dev, lib.nt_rank_metric_long, _ptr(scores), _ptr(targets), _ptr(m), n, t, _ptr(out), _ptr(workspace),
          0 if workspace is None else workspace.numel(), _stream(dev))
     return out
+
+
+# ------------------------------------------------------------------------------------ the fused MLP head
+def mlp_head_supported(x_dtype: torch.dtype, param_dtype: torch.dtype, dims) -> bool:
+    """Whether nt_mlp_head_forward takes this chain of widths (in, hidden..., out) and these dtypes: the
+    library's own statement of its limits (nt_mlp_head_supported)."""
+    if x_dtype not in _DTYPE_CODES or param_dtype not in _DTYPE_CODES or len(dims) < 2:
+        return False
+    arr = (ctypes.c_int64 * len(dims))(*[int(d) for d in dims])
+    return bool(_lib.load().nt_mlp_head_supported(_DTYPE_CODES[x_dtype], _DTYPE_CODES[param_dtype], len(dims) - 1,
+                                                  arr))
+
+
+def mlp_head(x: Tensor, weights, biases, act: tuple[int, float], out_dtype: torch.dtype | None = None) -> Tensor:
+    """y = L_n(act(... act(L_1(x)) ...)) in one launch (nt_mlp_head_forward), L_i = nn.Linear with weights[i]
+    ([out, in], contiguous) and biases[i] (or None); ``act`` is one ``act_code`` pair for the whole chain.
+    x: (..., in) with a unit last stride; the leading dimensions flatten to rows, which may sit a pitch apart
+    (a column slice of a wider tensor).  ``out_dtype`` picks the instance: float32 (the default for fp32 x and
+    fp32 parameters: the exact fp32 MFMA chain) or bfloat16 (x and parameters fp32 or bf16, rounded to bf16 as
+    loaded, bf16 between the layers: what the modules give under bf16 autocast).  Inference forward only: no
+    autograd graph is recorded."""
+    weights, biases = list(weights), list(biases)
+    if not weights or len(biases) != len(weights):
+        raise ValueError(f"{len(weights)} weights and {len(biases)} biases (one bias or None per weight, at least one)")
+    dev = _require_device(x, *weights, *biases)
+    if x.dtype not in _DTYPE_CODES:
+        raise TypeError(f"x must be float32 or bfloat16, got {x.dtype}")
+    pdt = weights[0].dtype
+    dims = [weights[0].shape[1] if weights[0].dim() == 2 else -1]
+    for i, (W, b) in enumerate(zip(weights, biases)):
+        _require_feat(f"weights[{i}]", W, pdt)
+        if W.dim() != 2 or W.shape[1] != dims[-1]:
+            raise ValueError(f"weights[{i}] must be out x {dims[-1]}, got {tuple(W.shape)}")
+        dims.append(W.shape[0])
+        if b is not None:
+            _require_feat(f"biases[{i}]", b, pdt)
+            if tuple(b.shape) != (W.shape[0],):
+                raise ValueError(f"biases[{i}] must have shape ({W.shape[0]},), got {tuple(b.shape)}")
+    if x.dim() < 1 or x.shape[-1] != dims[0]:
+        raise ValueError(f"x must be (..., {dims[0]}), got {tuple(x.shape)}")
+    if out_dtype is None:
+        out_dtype = torch.float32 if x.dtype == pdt == torch.float32 else torch.bfloat16
+    if out_dtype not in _DTYPE_CODES or (out_dtype == torch.float32 and not x.dtype == pdt == torch.float32):
+        raise TypeError(f"out_dtype {out_dtype} with {x.dtype} x and {pdt} parameters (float32 takes fp32 throughout)")
+    if not mlp_head_supported(x.dtype, pdt, dims):
+        raise ValueError(f"mlp_head does not take the widths {dims} (nt_mlp_head_supported)")
+    lead = tuple(x.shape[:-1])
+    rows2d = x.reshape(-1, dims[0])  # a view wherever the leading dimensions flatten without a copy
+    rows = rows2d.shape[0]
+    pitch = rows2d.stride(0) if rows > 1 else dims[0]
+    if (dims[0] > 1 and rows2d.stride(1) != 1) or pitch < dims[0] or (
+            pitch != dims[0] and pitch * x.element_size() % 16):
+        raise ValueError("x must have a unit last stride and rows that are contiguous or a multiple of 16 bytes "
+                         f"apart, got strides {tuple(x.stride())}")
+    out = torch.empty(rows, dims[-1], dtype=out_dtype, device=dev)
+    if rows == 0:
+        return out.view(*lead, dims[-1])
+    n = len(weights)
+    Wp = (ctypes.c_void_p * n)(*[W.data_ptr() for W in weights])
+    bp = (ctypes.c_void_p * n)(*[_ptr(b) for b in biases])
+    darr = (ctypes.c_int64 * (n + 1))(*dims)
+    _run(dev, _lib.load().nt_mlp_head_forward, _ptr(rows2d), _DTYPE_CODES[x.dtype], rows, pitch, n, Wp, bp,
+         _DTYPE_CODES[pdt], darr, int(act[0]), float(act[1]), _ptr(out), _DTYPE_CODES[out_dtype], _stream(dev))
+    return out.view(*lead, dims[-1])

@@ -1,21 +1,131 @@
 """``MLP`` head (reference ``notorch/nn/mlp.py:9-68``), SURVEY §8(f) row 4.
 
-The head runs on the readout's B x h rows (4096 x 300 at config 2: ~0.7 GFLOP per 300 x 300 layer), a
-plain dense GEMM that PyTorch-ROCm hands to hipBLASLt, so it is built from ``nn.Linear`` on purpose:
-no hand-written kernel would beat the library at this shape, and it is off the timed path.  What the
-drop-in needs is the same module tree: ``Linear, act, Dropout, Linear, ..., Linear`` (the dropout
-before the first layer and the activation after the last one are left out), optionally followed by
-``nn.Unflatten``, so the ``state_dict`` keys (``0.weight``, ``3.weight``, ...) and the output shape
-match the reference's.
+The module tree is the reference's: ``Linear, act, Dropout, Linear, ..., Linear`` (the dropout before the
+first layer and the activation after the last one are left out), optionally followed by ``nn.Unflatten``, so
+the ``state_dict`` keys (``0.weight``, ``3.weight``, ...) and the output shape match.  ``MLP(...)`` returns an
+``nn.Sequential`` subclass, :class:`MLPHead`, whose ``forward`` has two routes (``mlp_route``):
+
+* ``"kernel"``: the inference forward of the whole chain in ONE launch of ``nt_mlp_head_forward``
+  (``csrc/mlp_head.hip``): 16 rows per workgroup, their activations in LDS from layer to layer, weights read
+  in ``nn.Linear``'s own layout.  fp32 throughout runs the exact fp32 MFMA chain; under
+  ``torch.autocast("cuda", dtype=torch.bfloat16)`` the bf16 instance rounds where autocast's ``nn.Linear``
+  and activation round, and returns bf16.  ``Unflatten`` stays a view of the kernel's output.
+* ``"torch"``: ``nn.Sequential.forward``, bit for bit what it was.  Training through the head (an autograd
+  graph is needed, or dropout is active) always takes it: the kernel keeps no activations for a backward.  So
+  does anything the kernel route does not state: an edited child list, hooks on a child, other dtypes, an
+  autocast of another dtype, widths beyond ``nt_mlp_head_supported``, a CPU input.
+
+Knob ``NT_MLP`` (read per call): ``kernel`` takes the kernel wherever the route allows, ``torch`` never;
+unset, the kernel runs where ``tools/mlp_bench.py`` measured it ahead of the torch route in every run by
+more than that route's spread: 1 to 4096 rows, widths up to 300, two or three linear layers
+(``MLP_KERNEL_ROWS`` / ``MLP_KERNEL_MAX_WIDTH`` / ``MLP_KERNEL_LAYERS``; DESIGN.md §4 has the table).  At 32768
+rows the library GEMMs are ahead, so large batches stay on them.
 """
 from __future__ import annotations
 
+import os
 from collections.abc import Sequence
 from math import prod
 
+import torch
 import torch.nn as nn
 
+from notorch_amd import kernels as K
+from notorch_amd.nn.gnn import _engine
+
 DEFAULT_HIDDEN_DIM = 256  # notorch/conf.py:11
+
+# Where the kernel is the default (NT_MLP unset): row counts lo <= rows <= hi, for fp32 and for bf16 autocast,
+# the widest layer (input included) and the numbers of linear layers it was measured at.  (0, 0): nowhere.
+# From tools/mlp_bench.py (profiles/mlp_head/mlp_bench.jsonl): ahead of the torch route at 64, 512 and 4096
+# rows in every run (1.2x to 1.8x), behind it at 32768 (0.4x to 0.65x: a 16-row tile re-reads W per tile).
+MLP_KERNEL_ROWS: dict = {"fp32": (1, 4096), "bf16": (1, 4096)}
+MLP_KERNEL_MAX_WIDTH = 300
+MLP_KERNEL_LAYERS = (2, 3)
+
+__all__ = ["MLP", "MLPHead", "mlp_route", "DEFAULT_HIDDEN_DIM", "MLP_KERNEL_ROWS", "MLP_KERNEL_MAX_WIDTH",
+           "MLP_KERNEL_LAYERS"]
+
+
+def mlp_route(device_type: str, chain_ok: bool, hooks: bool, dropout_active: bool, needs_grad: bool,
+              x_dtype: torch.dtype, param_dtype: torch.dtype | None, autocast: str, supported: bool,
+              rows: int, widest: int, nlayers: int, knob: str = "") -> str:
+    """``"kernel"`` or ``"torch"`` for one forward of the head; pure, so it is tested without a GPU.
+    ``chain_ok``: the children are still ``Linear, (act, Dropout, Linear)*, [Unflatten]`` with one shared
+    activation that has a kernel code.  ``param_dtype``: the dtype all parameters share, None if they differ.
+    ``autocast``: ``""`` (off), ``"bf16"`` or ``"other"``.  ``supported``: ``nt_mlp_head_supported``.
+    ``rows``, ``widest`` (the widest layer, input included) and ``nlayers`` (linear layers) only matter to the
+    measured default.  ``knob`` is the value of ``NT_MLP``."""
+    if knob == "torch" or device_type != "cuda" or not chain_ok or hooks or dropout_active or needs_grad:
+        return "torch"
+    if autocast == "bf16":
+        mode = "bf16"
+        if x_dtype not in (torch.float32, torch.bfloat16) or param_dtype not in (torch.float32, torch.bfloat16):
+            return "torch"
+    elif autocast == "" and x_dtype == param_dtype == torch.float32:
+        mode = "fp32"
+    else:
+        return "torch"
+    if not supported:
+        return "torch"
+    if knob == "kernel":
+        return "kernel"
+    lo, hi = MLP_KERNEL_ROWS[mode]
+    measured = lo <= rows <= hi and rows > 0 and widest <= MLP_KERNEL_MAX_WIDTH and nlayers in MLP_KERNEL_LAYERS
+    return "kernel" if measured else "torch"
+
+
+class MLPHead(nn.Sequential):
+    """The ``nn.Sequential`` that ``MLP`` builds, with the fused inference route (module docstring)."""
+
+    def _chain(self):
+        """(linears, activation code) if the children are still the chain ``MLP`` built, else None."""
+        mods = list(self)
+        if mods and type(mods[-1]) is nn.Unflatten:
+            mods.pop()
+        if len(mods) % 3 != 1 or any(type(m) is not nn.Linear for m in mods[0::3]):
+            return None
+        acts, drops = mods[1::3], mods[2::3]
+        if any(a is not acts[0] for a in acts) or any(type(d) is not nn.Dropout for d in drops):
+            return None
+        try:
+            code = K.act_code(acts[0]) if acts else (0, 0.0)
+        except NotImplementedError:
+            return None
+        return mods[0::3], code
+
+    def forward(self, input):
+        knob = os.environ.get("NT_MLP", "")
+        if knob == "torch" or not isinstance(input, torch.Tensor) or input.device.type != "cuda" or input.dim() < 1:
+            return super().forward(input)
+        chain = self._chain()
+        linears = chain[0] if chain else []
+        params = [p for m in linears for p in (m.weight, m.bias) if p is not None]
+        dtypes = {p.dtype for p in params}
+        pdt = dtypes.pop() if len(dtypes) == 1 else None
+        dims = [linears[0].in_features, *(m.out_features for m in linears)] if linears else [0, 0]
+        if torch.is_autocast_enabled("cuda"):
+            autocast = "bf16" if _engine.autocast_bf16(input.device) else "other"
+        else:
+            autocast = ""
+        route = mlp_route(
+            input.device.type, chain is not None and input.shape[-1] == dims[0],
+            any(m._forward_hooks or m._forward_pre_hooks for m in self),
+            self.training and any(type(m) is nn.Dropout and m.p > 0 for m in self),
+            torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in params)),
+            input.dtype, pdt, autocast,
+            chain is not None and pdt is not None and K.mlp_head_supported(input.dtype, pdt, dims),
+            input.numel() // max(input.shape[-1], 1), max(dims), len(linears), knob)
+        if route != "kernel":
+            return super().forward(input)
+        x = input  # rows a whole number of 16-byte pieces apart go as they are (a column slice); else one copy
+        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= dims[0]
+                and x.stride(0) * x.element_size() % 16 == 0):
+            x = x.contiguous()
+        out = K.mlp_head(x, [m.weight for m in linears], [m.bias for m in linears], chain[1],
+                         out_dtype=torch.bfloat16 if autocast == "bf16" else torch.float32)
+        last = self[len(self) - 1]
+        return last(out) if type(last) is nn.Unflatten else out
 
 
 def MLP(
@@ -38,7 +148,7 @@ def MLP(
         if k > 0:  # between two linear layers: activation, then dropout
             mods += [act, drop]
         mods.append(nn.Linear(d_in, d_out))
-    mlp = nn.Sequential(*mods)
+    mlp = MLPHead(*mods)
     if shape is not None:
         mlp.append(nn.Unflatten(-1, shape))
     return mlp
