@@ -369,6 +369,48 @@ NT_API int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int64_t
                                const void* const* W, const void* const* b, int param_dtype, const int64_t* dims,
                                int act, float act_alpha, void* out, int out_dtype, void* stream);
 
+/*
+ * Training through that head (csrc/mlp_head.hip, csrc/mlp_head_train.hip; additive to ABI 8).
+ *
+ * nt_mlp_head_forward_train is nt_mlp_head_forward (same arguments, same checks, same values in out) which also
+ * stores every hidden layer's pre-activation z_l (after the bias and, in the bf16 instance, its rounding to bf16):
+ * saved is a host array of nlayers - 1 device pointers (NULL is accepted for nlayers == 1), saved[l] a contiguous
+ * rows x dims[l + 1] buffer of saved_dtype, which must be out_dtype.  nt_last_kernel reports "mlp_head_train_f32"
+ * or "mlp_head_train_bf16".
+ *
+ * nt_mlp_head_backward computes, from dy (rows x dims[nlayers], contiguous, `dtype`), x, the saved z and W:
+ *   dx     rows x dims[0] contiguous, x_dtype; NULL: not computed
+ *   dW[l]  dims[l+1] x dims[l] contiguous, param_dtype;  db[l]  dims[l+1], param_dtype (db, or an entry: NULL, none)
+ * in at most three launches whatever the depth: the dX chain (16 rows per workgroup, dZ in LDS from layer to layer,
+ * dZ_{l-1} = (dZ_l W_l) act'(z_{l-1})), one launch for every dW_l = dZ_l^T a_{l-1} and db_l over a work list of
+ * (layer, tile, row chunk) items, a_l = act(z_l) recomputed, and, when the rows make more than one chunk, a reduce
+ * of the chunks' fp32 partials in chunk order.  No atomics: two calls return the same bits.  `dtype` selects the
+ * instance as out_dtype does in the forward: NT_F32 (fp32 x and parameters, v_mfma_f32_16x16x4_f32) or NT_BF16
+ * (dy, saved and the dZ between layers bf16, rounded where autocast's modules round; x and the parameters NT_F32
+ * or NT_BF16 each; v_mfma_f32_16x16x32_bf16 with fp32 accumulation; dW / db written from fp32 without a bf16
+ * rounding for fp32 parameters).  workspace: nt_mlp_head_backward_workspace(rows, nlayers, dims, dtype) bytes of
+ * caller-owned device memory at a multiple of 16 bytes (dZ of the hidden layers and the partials; -1 for bad
+ * sizes; NULL is accepted where it is 0).  nt_mlp_head_train_supported states the limits of both calls once; they
+ * are nt_mlp_head_supported's (the chain's two gradient tiles are the forward's two activation tiles; the weight
+ * gradient stages 20 KiB whatever the widths).
+ * Checked on the host before any device call: NULL dy / x / W / W[l] / dims / dW / dW[l] / saved[l], nlayers
+ * outside 1..8, rows < 0 or above 2^31, a dims entry < 1, an act code outside NT_ACT_*, the x_pitch rules of the
+ * forward, a missing, misaligned or short workspace (NT_EINVAL); another dtype, an fp32 dy with a bf16 operand,
+ * widths beyond the limits (NT_EUNSUPPORTED).  rows == 0 launches none of the three and fills dW / db with zeros.
+ * nt_last_kernel reports "mlp_head_backward_f32" or "mlp_head_backward_bf16".  Stream-ordered; nothing is
+ * allocated or read back.
+ */
+NT_API int nt_mlp_head_train_supported(int x_dtype, int param_dtype, int nlayers, const int64_t* dims);
+NT_API int nt_mlp_head_forward_train(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
+                                     const void* const* W, const void* const* b, int param_dtype,
+                                     const int64_t* dims, int act, float act_alpha, void* out, int out_dtype,
+                                     void* const* saved, int saved_dtype, void* stream);
+NT_API int64_t nt_mlp_head_backward_workspace(int64_t rows, int nlayers, const int64_t* dims, int dtype);
+NT_API int nt_mlp_head_backward(const void* dy, int dtype, const void* x, int x_dtype, int64_t rows, int64_t x_pitch,
+                                int nlayers, const void* const* saved, const void* const* W, int param_dtype,
+                                const int64_t* dims, int act, float act_alpha, void* dx, void* const* dW,
+                                void* const* db, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

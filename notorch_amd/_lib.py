@@ -222,6 +222,21 @@ EXT_SIGNATURES: dict[str, tuple] = {
     "nt_mlp_head_forward": (
         _c_int, [_vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_f32, _vp, _c_int, _vp],
     ),
+    # training through it (csrc/mlp_head_train.hip): the forward's arguments + saved[nlayers - 1], saved_dtype
+    "nt_mlp_head_train_supported": (_c_int, [_c_int, _c_int, _c_int, _vp]),
+    "nt_mlp_head_forward_train": (
+        _c_int,
+        [_vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_f32, _vp, _c_int, _vp, _c_int, _vp],
+    ),
+    # rows, nlayers, dims, dtype
+    "nt_mlp_head_backward_workspace": (_c_i64, [_c_i64, _c_int, _vp, _c_int]),
+    # dy, dtype, x, x_dtype, rows, x_pitch, nlayers, saved, W, param_dtype, dims, act, alpha, dx | NULL, dW[], db[],
+    # workspace, workspace_bytes
+    "nt_mlp_head_backward": (
+        _c_int,
+        [_vp, _c_int, _vp, _c_int, _c_i64, _c_i64, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_f32, _vp, _vp, _vp, _vp,
+         _c_i64, _vp],
+    ),
 }
 
 # kind codes of nt_task_loss (include/notorch_amd_train.h)

@@ -22,32 +22,7 @@
 
 namespace nt {
 
-__device__ __forceinline__ float act_grad(float x, int act, float alpha) {
-  switch (act) {
-    case NT_ACT_RELU: return x > 0.f ? 1.f : 0.f;
-    case NT_ACT_LEAKY_RELU: return x > 0.f ? 1.f : alpha;
-    case NT_ACT_ELU: return x > 0.f ? 1.f : alpha * expf(x);
-    case NT_ACT_GELU: {
-      const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
-      const float pdf = 0.39894228040143268f * expf(-0.5f * x * x);
-      return cdf + x * pdf;
-    }
-    case NT_ACT_SILU: {
-      const float s = 1.f / (1.f + expf(-x));
-      return s * (1.f + x * (1.f - s));
-    }
-    case NT_ACT_TANH: {
-      const float t = tanhf(x);
-      return 1.f - t * t;
-    }
-    case NT_ACT_SIGMOID: {
-      const float s = 1.f / (1.f + expf(-x));
-      return s * (1.f - s);
-    }
-    default: return 1.f;
-  }
-}
-
+// act_grad: common.hpp
 template <int ACT>
 __device__ __forceinline__ float act_grad_t(float x, int act, float alpha) {
   if constexpr (ACT == NT_ACT_IDENTITY) return 1.f;

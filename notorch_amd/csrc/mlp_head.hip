@@ -1,5 +1,7 @@
 // The MLP predictor head (nn/mlp.py) in one launch: y = L_n(act(... act(L_1(x)) ...)), L_i(v) = v W_i^T + b_i,
-// up to 8 linear layers, inference forward only.
+// up to 8 linear layers: the inference forward, and the training forward (SAVE), which is the same chain and also
+// stores every hidden layer's pre-activation z_l (after the bias and, in the bf16 instance, the rounding) for the
+// backward of csrc/mlp_head_train.hip.
 //
 // Work split.  A workgroup (4 waves) owns a tile of R = 16 rows of x, one MFMA row tile: B = 4096 rows are 256
 // tiles, one per CU of the chip (R = 32 would leave half of it idle, R = 64 three quarters).  Tiles beyond the
@@ -33,7 +35,7 @@
 // width sits in the two LDS tiles: 2 * 16 rows * (64 ceil(w / 16) + 32) bytes <= 160 KiB = 163840 in fp32, so
 // ceil(w / 16) <= 79 and w <= 1264 (1265 takes 164864 bytes).  The bf16 tiles take half of that; one bound
 // serves both instances.
-#include "common.hpp"
+#include "mlp_frag.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -44,24 +46,10 @@ namespace nt {
 int cu_count();  // csrc/tile_plan.hip: the current device's CU count, queried once per device
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short bf16_t;  // raw bf16 storage
-
-constexpr int kRows = 16;  // R
-constexpr int kWaves = 4, kThreads = 64 * kWaves;
-constexpr int kCT = 4;  // column tiles a wave accumulates on one A fragment
-constexpr int kMaxLayers = 8;
-constexpr int64_t kLds = 160 * 1024;
-constexpr int64_t kMaxIn = 8192, kMaxWidth = 1264;
-
-__device__ __forceinline__ bf16_t f2bf(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }
-__device__ __forceinline__ float bf2f(bf16_t u) { return __uint_as_float((unsigned)u << 16); }
-__device__ __forceinline__ float rbf(float x) { return bf2f(f2bf(x)); }
-
 struct MlpLayer {
   const void* W;  // [out, in]
   const void* b;  // [out] or NULL
+  void* z;        // SAVE: [rows, out] pre-activations of a hidden layer, in the instance's dtype
   int in, out;
 };
 
@@ -77,65 +65,9 @@ struct MlpArgs {
   unsigned w_vec;  // bit l: so do the rows of layer l's W
 };
 
-// bytes of an LDS row that holds w activations: whole 64-byte k steps and the bank padding
-inline int lds_row_bytes(int64_t w, bool bf) { return (int)(bf ? (w + 31) / 32 * 64 + 16 : (w + 15) / 16 * 64 + 32); }
-
-// A lane's 16-byte fragment of the k step at k (4 floats, or 8 bf16) from a row of K elements in global memory;
-// a NULL row (past the rows of x, or the columns of W) and k past K are zeros.
-template <bool BF, typename T>
-__device__ __forceinline__ uint4 load_frag(const T* __restrict__ row, int k, int K, bool vec) {
-  if (row == nullptr || k >= K) return make_uint4(0u, 0u, 0u, 0u);
-  if constexpr (sizeof(T) == 2) {
-    if (vec && k + 8 <= K) return *reinterpret_cast<const uint4*>(row + k);
-    unsigned v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = k + j < K ? row[k + j] : 0u;
-    return make_uint4(v[0] | v[1] << 16, v[2] | v[3] << 16, v[4] | v[5] << 16, v[6] | v[7] << 16);
-  } else {
-    constexpr int E = BF ? 8 : 4;
-    float v[E];
-#pragma unroll
-    for (int p = 0; p < E; p += 4) {
-      if (vec && k + p + 4 <= K) {
-        const float4 f = *reinterpret_cast<const float4*>(row + k + p);
-        v[p] = f.x, v[p + 1] = f.y, v[p + 2] = f.z, v[p + 3] = f.w;
-      } else {
-#pragma unroll
-        for (int j = p; j < p + 4; ++j) v[j] = k + j < K ? row[k + j] : 0.f;
-      }
-    }
-    if constexpr (BF) {
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (__bf16)v[j];
-      return __builtin_bit_cast(uint4, o);
-    } else {
-      return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-    }
-  }
-}
-
-template <bool BF>
-__device__ __forceinline__ void mma(f32x4& acc, const uint4& a, const uint4& b) {
-  if constexpr (BF) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc,
-                                                  0, 0, 0);
-  } else {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ float load_param(const T* p) {
-  if constexpr (sizeof(T) == 2) return bf2f(*p);
-  else return *p;
-}
-
 // BF: the bf16 instance.  XT / PT: the storage of x and of the parameters (float, or bf16_t in the bf16 instance).
-template <bool BF, typename XT, typename PT>
+// SAVE: the training forward.
+template <bool BF, typename XT, typename PT, bool SAVE>
 __global__ __launch_bounds__(kThreads) void mlp_head_kernel(const MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int KS = BF ? 32 : 16;  // elements of a k step
@@ -220,6 +152,13 @@ __global__ __launch_bounds__(kThreads) void mlp_head_kernel(const MlpArgs a) {
                 else *o = v;
               }
             } else {
+              if constexpr (SAVE) {
+                if (col < N && r0 + row < a.rows) {
+                  OT* z = static_cast<OT*>(a.L[l].z) + (r0 + row) * N + col;
+                  if constexpr (BF) *z = f2bf(v);
+                  else *z = v;
+                }
+              }
               v = col < N ? act_apply(v, a.act, a.alpha) : 0.f;
               OT* o = reinterpret_cast<OT*>(aout + row * a.lds_row) + col;
               if constexpr (BF) *o = f2bf(v);
@@ -233,17 +172,26 @@ __global__ __launch_bounds__(kThreads) void mlp_head_kernel(const MlpArgs a) {
   }
 }
 
-inline bool dtype_ok(int d) { return d == NT_F32 || d == NT_BF16; }
-
-template <bool BF, typename XT, typename PT>
+template <bool BF, typename XT, typename PT, bool SAVE>
 int launch(const MlpArgs& a, int grid, size_t lds, hipStream_t stream) {
-  auto kern = mlp_head_kernel<BF, XT, PT>;
+  auto kern = mlp_head_kernel<BF, XT, PT, SAVE>;
   if (lds > 64 * 1024)
     NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   kern<<<grid, kThreads, lds, stream>>>(a);
   NT_LAUNCH_CHECK();
-  set_last_kernel(BF ? "mlp_head_bf16" : "mlp_head_f32");
+  if (SAVE) set_last_kernel(BF ? "mlp_head_train_bf16" : "mlp_head_train_f32");
+  else set_last_kernel(BF ? "mlp_head_bf16" : "mlp_head_f32");
   return NT_OK;
+}
+
+template <bool SAVE>
+int dispatch(const MlpArgs& a, bool bf, int x_dtype, int param_dtype, int grid, size_t lds, hipStream_t stream) {
+  if (!bf) return launch<false, float, float, SAVE>(a, grid, lds, stream);
+  if (x_dtype == NT_F32)
+    return param_dtype == NT_F32 ? launch<true, float, float, SAVE>(a, grid, lds, stream)
+                                 : launch<true, float, bf16_t, SAVE>(a, grid, lds, stream);
+  return param_dtype == NT_F32 ? launch<true, bf16_t, float, SAVE>(a, grid, lds, stream)
+                               : launch<true, bf16_t, bf16_t, SAVE>(a, grid, lds, stream);
 }
 
 }  // namespace
@@ -259,10 +207,13 @@ extern "C" int nt_mlp_head_supported(int x_dtype, int param_dtype, int nlayers, 
   return 1;
 }
 
-extern "C" int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
-                                   const void* const* W, const void* const* b, int param_dtype, const int64_t* dims,
-                                   int act, float act_alpha, void* out, int out_dtype, void* stream_) {
-  using namespace nt;
+namespace nt {
+namespace {
+// the two forwards' checks and launch; train: the training forward, which fills saved[l] for every hidden layer
+int mlp_head_forward(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
+                     const void* const* W, const void* const* b, int param_dtype, const int64_t* dims, int act,
+                     float act_alpha, void* out, int out_dtype, bool train, void* const* saved, int saved_dtype,
+                     void* stream_) {
   clear_error();
   NT_REQUIRE(x && W && dims && out, NT_EINVAL, "NULL pointer (x, W, dims and out are required)");
   NT_REQUIRE(nlayers >= 1 && nlayers <= kMaxLayers, NT_EINVAL,
@@ -277,6 +228,12 @@ extern "C" int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int
   NT_REQUIRE(bf || (x_dtype == NT_F32 && param_dtype == NT_F32), NT_EUNSUPPORTED,
              "dtype: an fp32 out takes fp32 x and fp32 parameters (the bf16 instance writes bf16)");
   NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "act code " + std::to_string(act));
+  if (train) {
+    NT_REQUIRE(nlayers == 1 || saved, NT_EINVAL, "NULL pointer (saved: one buffer per hidden layer)");
+    for (int l = 0; l + 1 < nlayers; ++l)
+      NT_REQUIRE(saved[l], NT_EINVAL, "NULL pointer (saved[" + std::to_string(l) + "])");
+    NT_REQUIRE(saved_dtype == out_dtype, NT_EUNSUPPORTED, "dtype: saved pre-activations have the dtype of out");
+  }
   const int64_t xbytes = x_dtype == NT_BF16 ? 2 : 4, pbytes = param_dtype == NT_BF16 ? 2 : 4;
   NT_REQUIRE(x_pitch >= dims[0], NT_EINVAL,
              "x pitch " + std::to_string(x_pitch) + " below dims[0] = " + std::to_string(dims[0]));
@@ -290,7 +247,8 @@ extern "C" int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int
   MlpArgs a{};
   int64_t widest = 0;
   for (int l = 0; l < nlayers; ++l) {
-    a.L[l] = MlpLayer{W[l], b ? b[l] : nullptr, (int)dims[l], (int)dims[l + 1]};
+    a.L[l] = MlpLayer{W[l], b ? b[l] : nullptr, train && l + 1 < nlayers ? saved[l] : nullptr, (int)dims[l],
+                      (int)dims[l + 1]};
     if (aligned16(W[l]) && dims[l] * pbytes % 16 == 0) a.w_vec |= 1u << l;
     if (l + 1 < nlayers && dims[l + 1] > widest) widest = dims[l + 1];
   }
@@ -305,10 +263,23 @@ extern "C" int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int
   const int cus = cu_count() > 0 ? cu_count() : 256;
   const int grid = (int)std::min<int64_t>(ntiles, per_cu * cus);
   hipStream_t stream = as_stream(stream_);
-  if (!bf) return launch<false, float, float>(a, grid, lds, stream);
-  if (x_dtype == NT_F32)
-    return param_dtype == NT_F32 ? launch<true, float, float>(a, grid, lds, stream)
-                                 : launch<true, float, bf16_t>(a, grid, lds, stream);
-  return param_dtype == NT_F32 ? launch<true, bf16_t, float>(a, grid, lds, stream)
-                               : launch<true, bf16_t, bf16_t>(a, grid, lds, stream);
+  return train ? dispatch<true>(a, bf, x_dtype, param_dtype, grid, lds, stream)
+               : dispatch<false>(a, bf, x_dtype, param_dtype, grid, lds, stream);
+}
+}  // namespace
+}  // namespace nt
+
+extern "C" int nt_mlp_head_forward(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
+                                   const void* const* W, const void* const* b, int param_dtype, const int64_t* dims,
+                                   int act, float act_alpha, void* out, int out_dtype, void* stream) {
+  return nt::mlp_head_forward(x, x_dtype, rows, x_pitch, nlayers, W, b, param_dtype, dims, act, act_alpha, out,
+                              out_dtype, false, nullptr, 0, stream);
+}
+
+extern "C" int nt_mlp_head_forward_train(const void* x, int x_dtype, int64_t rows, int64_t x_pitch, int nlayers,
+                                         const void* const* W, const void* const* b, int param_dtype,
+                                         const int64_t* dims, int act, float act_alpha, void* out, int out_dtype,
+                                         void* const* saved, int saved_dtype, void* stream) {
+  return nt::mlp_head_forward(x, x_dtype, rows, x_pitch, nlayers, W, b, param_dtype, dims, act, act_alpha, out,
+                              out_dtype, true, saved, saved_dtype, stream);
 }

@@ -66,6 +66,9 @@ __all__ = [
     "rank_metric_max_n",
     "mlp_head_supported",
     "mlp_head",
+    "mlp_head_train_supported",
+    "mlp_head_train_forward",
+    "mlp_head_backward",
 ]
 
 
@@ -1867,15 +1870,9 @@ def mlp_head_supported(x_dtype: torch.dtype, param_dtype: torch.dtype, dims) -> 
                                                   arr))
 
 
-def mlp_head(x: Tensor, weights, biases, act: tuple[int, float], out_dtype: torch.dtype | None = None) -> Tensor:
-    """y = L_n(act(... act(L_1(x)) ...)) in one launch (nt_mlp_head_forward), L_i = nn.Linear with weights[i]
-    ([out, in], contiguous) and biases[i] (or None); ``act`` is one ``act_code`` pair for the whole chain.
-    x: (..., in) with a unit last stride; the leading dimensions flatten to rows, which may sit a pitch apart
-    (a column slice of a wider tensor).  ``out_dtype`` picks the instance: float32 (the default for fp32 x and
-    fp32 parameters: the exact fp32 MFMA chain) or bfloat16 (x and parameters fp32 or bf16, rounded to bf16 as
-    loaded, bf16 between the layers: what the modules give under bf16 autocast).  Inference forward only: no
-    autograd graph is recorded."""
-    weights, biases = list(weights), list(biases)
+def _mlp_head_args(x: Tensor, weights, biases, out_dtype, supported, what: str):
+    """The argument checks that mlp_head and the training wrappers share.  Returns (device, parameter dtype, dims,
+    x as rows, rows, row pitch, leading shape, out_dtype)."""
     if not weights or len(biases) != len(weights):
         raise ValueError(f"{len(weights)} weights and {len(biases)} biases (one bias or None per weight, at least one)")
     dev = _require_device(x, *weights, *biases)
@@ -1898,8 +1895,8 @@ def mlp_head(x: Tensor, weights, biases, act: tuple[int, float], out_dtype: torc
         out_dtype = torch.float32 if x.dtype == pdt == torch.float32 else torch.bfloat16
     if out_dtype not in _DTYPE_CODES or (out_dtype == torch.float32 and not x.dtype == pdt == torch.float32):
         raise TypeError(f"out_dtype {out_dtype} with {x.dtype} x and {pdt} parameters (float32 takes fp32 throughout)")
-    if not mlp_head_supported(x.dtype, pdt, dims):
-        raise ValueError(f"mlp_head does not take the widths {dims} (nt_mlp_head_supported)")
+    if not supported(x.dtype, pdt, dims):
+        raise ValueError(f"{what} does not take the widths {dims} (nt_{what}_supported)")
     lead = tuple(x.shape[:-1])
     rows2d = x.reshape(-1, dims[0])  # a view wherever the leading dimensions flatten without a copy
     rows = rows2d.shape[0]
@@ -1908,13 +1905,93 @@ def mlp_head(x: Tensor, weights, biases, act: tuple[int, float], out_dtype: torc
             pitch != dims[0] and pitch * x.element_size() % 16):
         raise ValueError("x must have a unit last stride and rows that are contiguous or a multiple of 16 bytes "
                          f"apart, got strides {tuple(x.stride())}")
+    return dev, pdt, dims, rows2d, rows, pitch, lead, out_dtype
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * max(len(ts), 1))(*[_ptr(t) for t in ts])
+
+
+def mlp_head(x: Tensor, weights, biases, act: tuple[int, float], out_dtype: torch.dtype | None = None) -> Tensor:
+    """y = L_n(act(... act(L_1(x)) ...)) in one launch (nt_mlp_head_forward), L_i = nn.Linear with weights[i]
+    ([out, in], contiguous) and biases[i] (or None); ``act`` is one ``act_code`` pair for the whole chain.
+    x: (..., in) with a unit last stride; the leading dimensions flatten to rows, which may sit a pitch apart
+    (a column slice of a wider tensor).  ``out_dtype`` picks the instance: float32 (the default for fp32 x and
+    fp32 parameters: the exact fp32 MFMA chain) or bfloat16 (x and parameters fp32 or bf16, rounded to bf16 as
+    loaded, bf16 between the layers: what the modules give under bf16 autocast).  Inference forward only: no
+    autograd graph is recorded."""
+    weights, biases = list(weights), list(biases)
+    dev, pdt, dims, rows2d, rows, pitch, lead, out_dtype = _mlp_head_args(x, weights, biases, out_dtype,
+                                                                          mlp_head_supported, "mlp_head")
     out = torch.empty(rows, dims[-1], dtype=out_dtype, device=dev)
     if rows == 0:
         return out.view(*lead, dims[-1])
     n = len(weights)
-    Wp = (ctypes.c_void_p * n)(*[W.data_ptr() for W in weights])
-    bp = (ctypes.c_void_p * n)(*[_ptr(b) for b in biases])
     darr = (ctypes.c_int64 * (n + 1))(*dims)
-    _run(dev, _lib.load().nt_mlp_head_forward, _ptr(rows2d), _DTYPE_CODES[x.dtype], rows, pitch, n, Wp, bp,
-         _DTYPE_CODES[pdt], darr, int(act[0]), float(act[1]), _ptr(out), _DTYPE_CODES[out_dtype], _stream(dev))
+    _run(dev, _lib.load().nt_mlp_head_forward, _ptr(rows2d), _DTYPE_CODES[x.dtype], rows, pitch, n,
+         _ptr_array(weights), _ptr_array(biases), _DTYPE_CODES[pdt], darr, int(act[0]), float(act[1]), _ptr(out),
+         _DTYPE_CODES[out_dtype], _stream(dev))
     return out.view(*lead, dims[-1])
+
+
+def mlp_head_train_supported(x_dtype: torch.dtype, param_dtype: torch.dtype, dims) -> bool:
+    """Whether the training forward and the backward take this chain of widths and these dtypes
+    (nt_mlp_head_train_supported)."""
+    if x_dtype not in _DTYPE_CODES or param_dtype not in _DTYPE_CODES or len(dims) < 2:
+        return False
+    arr = (ctypes.c_int64 * len(dims))(*[int(d) for d in dims])
+    return bool(_lib.load().nt_mlp_head_train_supported(_DTYPE_CODES[x_dtype], _DTYPE_CODES[param_dtype],
+                                                        len(dims) - 1, arr))
+
+
+def mlp_head_train_forward(x: Tensor, weights, biases, act: tuple[int, float],
+                           out_dtype: torch.dtype | None = None) -> tuple[Tensor, list[Tensor]]:
+    """``mlp_head`` that also keeps what the backward needs (nt_mlp_head_forward_train): returns (y, saved),
+    saved[l] the rows x out_l pre-activation of hidden layer l in ``out_dtype``.  Arguments as ``mlp_head``."""
+    weights, biases = list(weights), list(biases)
+    dev, pdt, dims, rows2d, rows, pitch, lead, out_dtype = _mlp_head_args(x, weights, biases, out_dtype,
+                                                                          mlp_head_train_supported, "mlp_head_train")
+    out = torch.empty(rows, dims[-1], dtype=out_dtype, device=dev)
+    saved = [torch.empty(rows, d, dtype=out_dtype, device=dev) for d in dims[1:-1]]
+    if rows > 0:
+        n = len(weights)
+        darr = (ctypes.c_int64 * (n + 1))(*dims)
+        code = _DTYPE_CODES[out_dtype]
+        _run(dev, _lib.load().nt_mlp_head_forward_train, _ptr(rows2d), _DTYPE_CODES[x.dtype], rows, pitch, n,
+             _ptr_array(weights), _ptr_array(biases), _DTYPE_CODES[pdt], darr, int(act[0]), float(act[1]), _ptr(out),
+             code, _ptr_array(saved), code, _stream(dev))
+    return out.view(*lead, dims[-1]), saved
+
+
+def mlp_head_backward(dy: Tensor, x: Tensor, saved, weights, has_bias, act: tuple[int, float],
+                      need_dx: bool = True) -> tuple[Tensor | None, list[Tensor], list[Tensor | None]]:
+    """The backward of ``mlp_head_train_forward`` (nt_mlp_head_backward; at most three launches): dy (..., out),
+    contiguous, in the forward's ``out_dtype``; x, weights and ``act`` as given to the forward; ``saved`` as it
+    returned them; has_bias[i]: layer i has a bias.  Returns (dx in x's dtype and shape, or None without
+    ``need_dx``; dW per layer; db per layer, None where has_bias[i] is false), the parameters' gradients in the
+    parameters' dtype.  Bit-reproducible."""
+    weights, saved, has_bias = list(weights), list(saved), [bool(h) for h in has_bias]
+    dev, pdt, dims, rows2d, rows, pitch, lead, dt = _mlp_head_args(
+        x, weights, [None] * len(has_bias), dy.dtype, mlp_head_train_supported, "mlp_head_train")
+    _require_device(dy, *saved)
+    if tuple(dy.shape) != (*lead, dims[-1]) or not dy.is_contiguous():
+        raise ValueError(f"dy must be contiguous {(*lead, dims[-1])}, got {tuple(dy.shape)}")
+    if len(saved) != len(weights) - 1:
+        raise ValueError(f"{len(saved)} saved pre-activations for {len(weights)} layers")
+    for i, z in enumerate(saved):
+        if z.dtype != dt or tuple(z.shape) != (rows, dims[i + 1]) or not z.is_contiguous():
+            raise ValueError(f"saved[{i}] must be contiguous {dt} {(rows, dims[i + 1])}")
+    n = len(weights)
+    dx = torch.empty(rows, dims[0], dtype=x.dtype, device=dev) if need_dx else None
+    dWs = [torch.empty_like(W) for W in weights]
+    dbs = [torch.empty(W.shape[0], dtype=pdt, device=dev) if h else None for W, h in zip(weights, has_bias)]
+    lib = _lib.load()
+    darr = (ctypes.c_int64 * (n + 1))(*dims)
+    ws_bytes = int(lib.nt_mlp_head_backward_workspace(rows, n, darr, _DTYPE_CODES[dt]))
+    if ws_bytes < 0:
+        raise ValueError(f"mlp_head_backward: bad sizes (rows {rows}, dims {dims})")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes > 0 else None
+    _run(dev, lib.nt_mlp_head_backward, _ptr(dy), _DTYPE_CODES[dt], _ptr(rows2d), _DTYPE_CODES[x.dtype], rows, pitch,
+         n, _ptr_array(saved), _ptr_array(weights), _DTYPE_CODES[pdt], darr, int(act[0]), float(act[1]), _ptr(dx),
+         _ptr_array(dWs), _ptr_array(dbs), _ptr(ws), ws_bytes, _stream(dev))
+    return (None if dx is None else dx.view(*lead, dims[0])), dWs, dbs

@@ -3,7 +3,8 @@
 The module tree is the reference's: ``Linear, act, Dropout, Linear, ..., Linear`` (the dropout before the
 first layer and the activation after the last one are left out), optionally followed by ``nn.Unflatten``, so
 the ``state_dict`` keys (``0.weight``, ``3.weight``, ...) and the output shape match.  ``MLP(...)`` returns an
-``nn.Sequential`` subclass, :class:`MLPHead`, whose ``forward`` has two routes (``mlp_route``):
+``nn.Sequential`` subclass, :class:`MLPHead`, whose ``forward`` has two routes (``mlp_route``) and, for a forward
+that needs an autograd graph, an opt-in third (``mlp_train_route``, below):
 
 * ``"kernel"``: the inference forward of the whole chain in ONE launch of ``nt_mlp_head_forward``
   (``csrc/mlp_head.hip``): 16 rows per workgroup, their activations in LDS from layer to layer, weights read
@@ -11,15 +12,26 @@ the ``state_dict`` keys (``0.weight``, ``3.weight``, ...) and the output shape m
   ``torch.autocast("cuda", dtype=torch.bfloat16)`` the bf16 instance rounds where autocast's ``nn.Linear``
   and activation round, and returns bf16.  ``Unflatten`` stays a view of the kernel's output.
 * ``"torch"``: ``nn.Sequential.forward``, bit for bit what it was.  Training through the head (an autograd
-  graph is needed, or dropout is active) always takes it: the kernel keeps no activations for a backward.  So
-  does anything the kernel route does not state: an edited child list, hooks on a child, other dtypes, an
-  autocast of another dtype, widths beyond ``nt_mlp_head_supported``, a CPU input.
+  graph is needed, or dropout is active) takes it unless ``NT_MLP_TRAIN=kernel`` is set: the inference kernel
+  keeps no activations for a backward.  So does anything the kernel route does not state: an edited child list,
+  hooks on a child, other dtypes, an autocast of another dtype, widths beyond ``nt_mlp_head_supported``, a CPU
+  input.
 
 Knob ``NT_MLP`` (read per call): ``kernel`` takes the kernel wherever the route allows, ``torch`` never;
 unset, the kernel runs where ``tools/mlp_bench.py`` measured it ahead of the torch route in every run by
 more than that route's spread: 1 to 4096 rows, widths up to 300, two or three linear layers
 (``MLP_KERNEL_ROWS`` / ``MLP_KERNEL_MAX_WIDTH`` / ``MLP_KERNEL_LAYERS``; DESIGN.md §4 has the table).  At 32768
 rows the library GEMMs are ahead, so large batches stay on them.
+
+Training on the kernels (knob ``NT_MLP_TRAIN``, read per call; opt-in).  With ``NT_MLP_TRAIN=kernel`` a forward that
+needs an autograd graph runs ``nt_mlp_head_forward_train`` (the same chain in one launch, which also stores every
+hidden layer's pre-activation) under a ``torch.autograd.Function`` whose backward is ``nt_mlp_head_backward``
+(``csrc/mlp_head_train.hip``): the dX chain in one launch, every ``dW`` / ``db`` in a second over one work list, and
+a fixed-order reduce of the row chunks' partials when there are several; at most three launches whatever the
+depth, bit-reproducible, no double backward.  ``mlp_train_route`` takes it only for a CUDA input, an intact chain
+without hooks, no active dropout (``p > 0`` in training stays on torch), fp32 throughout or bf16 autocast,
+``nt_mlp_head_train_supported`` and parameters that all require grad.  Unset, ``NT_MLP_TRAIN=torch`` or
+``NT_MLP=torch``: training is bit for bit what it was.  ``NT_MLP`` and ``mlp_route`` do not change meaning.
 """
 from __future__ import annotations
 
@@ -43,8 +55,8 @@ MLP_KERNEL_ROWS: dict = {"fp32": (1, 4096), "bf16": (1, 4096)}
 MLP_KERNEL_MAX_WIDTH = 300
 MLP_KERNEL_LAYERS = (2, 3)
 
-__all__ = ["MLP", "MLPHead", "mlp_route", "DEFAULT_HIDDEN_DIM", "MLP_KERNEL_ROWS", "MLP_KERNEL_MAX_WIDTH",
-           "MLP_KERNEL_LAYERS"]
+__all__ = ["MLP", "MLPHead", "mlp_route", "mlp_train_route", "DEFAULT_HIDDEN_DIM", "MLP_KERNEL_ROWS",
+           "MLP_KERNEL_MAX_WIDTH", "MLP_KERNEL_LAYERS"]
 
 
 def mlp_route(device_type: str, chain_ok: bool, hooks: bool, dropout_active: bool, needs_grad: bool,
@@ -75,8 +87,57 @@ def mlp_route(device_type: str, chain_ok: bool, hooks: bool, dropout_active: boo
     return "kernel" if measured else "torch"
 
 
+def mlp_train_route(device_type: str, chain_ok: bool, hooks: bool, dropout_active: bool, needs_grad: bool,
+                    all_params_grad: bool, x_dtype: torch.dtype, param_dtype: torch.dtype | None, autocast: str,
+                    supported: bool, train_knob: str = "", knob: str = "") -> str:
+    """``"kernel"`` (the training kernels) or ``"torch"`` for one forward that may need an autograd graph; pure.
+    Arguments as ``mlp_route``; ``all_params_grad``: every parameter requires grad; ``supported``:
+    ``nt_mlp_head_train_supported``; ``train_knob`` / ``knob``: the values of ``NT_MLP_TRAIN`` / ``NT_MLP``."""
+    if train_knob != "kernel" or knob == "torch" or not needs_grad or not all_params_grad:
+        return "torch"
+    if device_type != "cuda" or not chain_ok or hooks or dropout_active or not supported:
+        return "torch"
+    if autocast == "bf16":
+        ok = x_dtype in (torch.float32, torch.bfloat16) and param_dtype in (torch.float32, torch.bfloat16)
+    else:
+        ok = autocast == "" and x_dtype == param_dtype == torch.float32
+    return "kernel" if ok else "torch"
+
+
+def _kernel_rows(x: torch.Tensor, width: int) -> torch.Tensor:
+    """x as the kernels take it: rows a whole number of 16-byte pieces apart go as they are (a column slice);
+    anything else is copied once."""
+    if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= width and x.stride(0) * x.element_size() % 16 == 0):
+        x = x.contiguous()
+    return x
+
+
+class _MLPHeadTrain(torch.autograd.Function):
+    """The head's chain on the training kernels: forward(x, act, out_dtype, n, W_1..W_n, b_1..b_n (or None))."""
+
+    @staticmethod
+    def forward(ctx, x, act, out_dtype, n, *params):
+        weights, biases = params[:n], params[n:]
+        xk = _kernel_rows(x.detach(), weights[0].shape[1])
+        y, saved = K.mlp_head_train_forward(xk, [w.detach() for w in weights],
+                                            [None if b is None else b.detach() for b in biases], act, out_dtype)
+        ctx.save_for_backward(xk, *weights, *saved)
+        ctx.act, ctx.n, ctx.has_bias = act, n, [b is not None for b in biases]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        n = ctx.n
+        xk, weights, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + n], ctx.saved_tensors[1 + n:]
+        dx, dWs, dbs = K.mlp_head_backward(dy.contiguous(), xk, saved, weights, ctx.has_bias, ctx.act,
+                                           need_dx=ctx.needs_input_grad[0])
+        return (dx, None, None, None, *dWs, *dbs)
+
+
 class MLPHead(nn.Sequential):
-    """The ``nn.Sequential`` that ``MLP`` builds, with the fused inference route (module docstring)."""
+    """The ``nn.Sequential`` that ``MLP`` builds, with the fused inference route and the opt-in training route
+    (module docstring)."""
 
     def _chain(self):
         """(linears, activation code) if the children are still the chain ``MLP`` built, else None."""
@@ -108,22 +169,28 @@ class MLPHead(nn.Sequential):
             autocast = "bf16" if _engine.autocast_bf16(input.device) else "other"
         else:
             autocast = ""
-        route = mlp_route(
-            input.device.type, chain is not None and input.shape[-1] == dims[0],
-            any(m._forward_hooks or m._forward_pre_hooks for m in self),
-            self.training and any(type(m) is nn.Dropout and m.p > 0 for m in self),
-            torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in params)),
-            input.dtype, pdt, autocast,
-            chain is not None and pdt is not None and K.mlp_head_supported(input.dtype, pdt, dims),
-            input.numel() // max(input.shape[-1], 1), max(dims), len(linears), knob)
-        if route != "kernel":
-            return super().forward(input)
-        x = input  # rows a whole number of 16-byte pieces apart go as they are (a column slice); else one copy
-        if not (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= dims[0]
-                and x.stride(0) * x.element_size() % 16 == 0):
-            x = x.contiguous()
-        out = K.mlp_head(x, [m.weight for m in linears], [m.bias for m in linears], chain[1],
-                         out_dtype=torch.bfloat16 if autocast == "bf16" else torch.float32)
+        chain_ok = chain is not None and input.shape[-1] == dims[0]
+        hooks = any(m._forward_hooks or m._forward_pre_hooks for m in self)
+        dropout_active = self.training and any(type(m) is nn.Dropout and m.p > 0 for m in self)
+        needs_grad = torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in params))
+        out_dtype = torch.bfloat16 if autocast == "bf16" else torch.float32
+        train_knob = os.environ.get("NT_MLP_TRAIN", "")
+        if needs_grad and train_knob == "kernel" and mlp_train_route(
+                input.device.type, chain_ok, hooks, dropout_active, needs_grad,
+                all(p.requires_grad for p in params), input.dtype, pdt, autocast,
+                chain_ok and pdt is not None and K.mlp_head_train_supported(input.dtype, pdt, dims),
+                train_knob, knob) == "kernel":
+            out = _MLPHeadTrain.apply(input, chain[1], out_dtype, len(linears), *(m.weight for m in linears),
+                                      *(m.bias for m in linears))
+        else:
+            route = mlp_route(
+                input.device.type, chain_ok, hooks, dropout_active, needs_grad, input.dtype, pdt, autocast,
+                chain is not None and pdt is not None and K.mlp_head_supported(input.dtype, pdt, dims),
+                input.numel() // max(input.shape[-1], 1), max(dims), len(linears), knob)
+            if route != "kernel":
+                return super().forward(input)
+            out = K.mlp_head(_kernel_rows(input, dims[0]), [m.weight for m in linears], [m.bias for m in linears],
+                             chain[1], out_dtype=out_dtype)
         last = self[len(self) - 1]
         return last(out) if type(last) is nn.Unflatten else out
 

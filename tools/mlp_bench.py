@@ -14,8 +14,14 @@ call to the end of a device synchronise.  Per run and route the figure is the me
 Prints one JSON line per shape: per route the median over the runs' figures, the runs' figures, their run-to-run
 spread (max - min) and the spread over all rounds of all runs.  kernel_wins: in every run the kernel's wall
 figure is below the torch route's by more than that route's run-to-run spread, and so is its device figure.
+
+--train times a training step through the head instead: forward plus backward on a fixed dY (x requires grad;
+gradients are cleared outside the timed region), the head in .train() with NT_MLP_TRAIN=kernel
+(nt_mlp_head_forward_train + nt_mlp_head_backward) against the same plain nn.Sequential; B in {64, 512, 4096}.
+    python tools/mlp_bench.py --train --out profiles/mlp_head/mlp_train_bench.jsonl
 Fails without a GPU."""
 import argparse
+import contextlib
 import json
 import os
 import statistics
@@ -38,34 +44,54 @@ def child(args) -> int:
         print("mlp_bench: no GPU; a time measured without one means nothing", file=sys.stderr)
         return 2
     os.environ["NT_MLP"] = "kernel"
+    if args.train:
+        os.environ["NT_MLP_TRAIN"] = "kernel"
     from notorch_amd import _lib
     from notorch_amd.nn import MLP
 
     for dims in HEADS:
         torch.manual_seed(0)
-        head = MLP(dims[0], dims[-1], hidden_dim=dims[1], num_layers=len(dims) - 2).cuda().eval()
+        head = MLP(dims[0], dims[-1], hidden_dim=dims[1], num_layers=len(dims) - 2).cuda().train(args.train)
         plain = nn.Sequential(*head)  # the parent's head: the same children in a plain nn.Sequential
         for mode in ("fp32", "bf16"):
-            for rows in BATCHES:
-                x = torch.randn(rows, dims[0], device="cuda")
+            for rows in (BATCHES[:3] if args.train else BATCHES):
+                x = torch.randn(rows, dims[0], device="cuda", requires_grad=args.train)
+                dy = torch.randn(rows, dims[-1], device="cuda", dtype=torch.bfloat16 if mode == "bf16" else None)
                 routes = {"kernel": head, "torch": plain}
                 ctx = torch.autocast("cuda", dtype=torch.bfloat16, enabled=mode == "bf16")
-                with torch.no_grad(), ctx:
+                want = ("mlp_head_train_" if args.train else "mlp_head_") + ("bf16" if mode == "bf16" else "f32")
+
+                def call(mod):
+                    if args.train:
+                        with ctx:
+                            y = mod(x)
+                        y.backward(dy)
+                    else:
+                        mod(x)
+
+                def clear():
+                    x.grad = None
+                    head.zero_grad(set_to_none=True)
+
+                # inference: one autocast region around everything; training: around each forward only
+                with torch.set_grad_enabled(args.train), (contextlib.nullcontext() if args.train else ctx):
                     for name, mod in routes.items():
                         for _ in range(10):
-                            mod(x)
+                            call(mod)
                         if name == "kernel":
-                            assert _lib.load().nt_last_kernel().decode() == "mlp_head_" + ("bf16" if mode == "bf16" else "f32")
+                            assert _lib.load().nt_last_kernel().decode() == want
                     torch.cuda.synchronize()
                     dev = {n: [] for n in routes}
                     wall = {n: [] for n in routes}
                     for _ in range(args.rounds):
                         for name, mod in routes.items():
+                            clear()
+                            torch.cuda.synchronize()
                             start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                             t0 = time.perf_counter()
                             start.record()
                             for _ in range(args.calls):
-                                mod(x)
+                                call(mod)
                             stop.record()
                             torch.cuda.synchronize()
                             wall[name].append((time.perf_counter() - t0) * 1e3 / args.calls)
@@ -81,6 +107,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--out", default="")
+    ap.add_argument("--train", action="store_true", help="time forward + backward (NT_MLP_TRAIN=kernel)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
@@ -89,7 +116,7 @@ def main() -> int:
     runs = []  # per run: {(dims, mode, rows): row}
     for _ in range(args.runs):  # fresh processes, one at a time; this one never opens the GPU
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--rounds", str(args.rounds),
-                            "--calls", str(args.calls)], stdout=subprocess.PIPE, text=True, timeout=900)
+                            "--calls", str(args.calls)] + (["--train"] if args.train else []), stdout=subprocess.PIPE, text=True, timeout=900)
         if p.returncode != 0:
             return p.returncode
         rows = [json.loads(line) for line in p.stdout.splitlines() if line.startswith("{")]
