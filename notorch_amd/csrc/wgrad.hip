@@ -5,19 +5,37 @@
 //   dW    = G^T A          (h x h, reduced over all E edges)
 //   db    = sum_e G[e]
 //
-// Split-K over edges: a 1-D grid of (64 x 64 output tile, edge chunk) workgroups.  Each workgroup
+// Six kernels compute it, one per route (kRoutes below holds the same rows for the host side):
+//
+//   entry                    dtype  h                      kernel                  block  LDS      tile of dW   plan
+//   nt_dmpnn_weight_grad     fp32   any (dense, or > 320)  wgrad_kernel            256    24 KiB   64 x 64      4 slots / CU, ksplit % 8 == 0
+//   nt_dmpnn_weight_grad     fp32   <= 320, gathered       wgrad_wide_kernel       512    84 KiB   h x 128      1 slot / CU
+//   nt_dmpnn_weight_grad_fk  fp32   <= 320                 wgrad_fk_kernel         512    112 KiB  h x 128      1 slot / CU
+//   nt_dmpnn_weight_grad_fk  fp32   324 .. 8192, h % 4     wgrad_fk_wide_kernel    512    136 KiB  256 x 256    1 slot / CU
+//   nt_dmpnn_weight_grad     bf16   <= 512, even           wgrad_bf16_kernel       512    80 KiB   h x 128      1 slot / CU
+//   nt_dmpnn_weight_grad     bf16   520 .. 8192, h % 8     wgrad_bf16_wide_kernel  512    68 KiB   256 x 256    1 slot / CU
+//
+// What they share.  Split-K over edges: a 1-D grid of (tile of dW, edge chunk) workgroups, each walking
+// its chunk 32 edges at a time; split_k_plan picks the chunk count so that one round of workgroups fills
+// the machine.  The work id is remapped so that the tiles of one chunk run on one XCD (blocks b, b + n
+// share an XCD) and the chunk's G / S / H rows are fetched into that XCD's L2 once.  The (src, rev) of
+// the edges a wave gathers for are fetched a step ahead as one vector load and broadcast with readlane,
+// so no scalar-load round trip sits in front of the row gathers.  Every load is unconditional (rows
+// clamped to the chunk, columns to the row) and masked afterwards: a load whose value is used under a
+// condition gets sunk into a branch by the compiler, with a vmcnt(0) wait right behind it.  Partials
+// (and the bias partials of the j-block-0 workgroups) go to a workspace that wgrad_reduce2_kernel sums
+// in fixed order, so the result is deterministic.  Each kernel keeps its own argument block and writes
+// its prologue and epilogue out: one merged block, and shared inline helpers, each changed the generated
+// code of the kernels, and the merged block their speed (profiles/wgrad_refactor/).
+//
+// wgrad_kernel: a 1-D grid of (64 x 64 output tile, edge chunk) workgroups.  Each workgroup
 // walks its chunk 32 edges at a time: 256 threads load the 32 x 64 slab of G and of A (thread =
 // one column, 8 consecutive edges; each load instruction reads 64 consecutive floats of one row),
 // split every fp32 value into three bf16 parts once, and store them to a double-buffered LDS slab
 // laid out [part][edge group][column] in 16-B units, so both the writes and the MFMA fragment reads
 // are contiguous 1 KiB runs (no bank conflicts).  Wave w owns a 32 x 32 quadrant: 4 MFMA tiles x 6
-// bf16 products (a bf16x6 split: fp32-accurate) per 32 edges.
-// Partials (and the bias partials of the j-tile-0 workgroups) go to a workspace, reduced by a
-// second kernel in fixed order, so the result is deterministic.
-//
-// XCD-aware: all output tiles of one edge chunk run on one XCD (blocks b, b + n share an XCD), so
-// the chunk's G / S / H rows are fetched into that XCD's L2 once and read from there by the 25
-// (at h = 300) tiles.
+// bf16 products (a bf16x6 split: fp32-accurate) per 32 edges.  The other kernels are described above
+// their definitions.
 //
 // Algorithmic bytes per call: G and A operands E*h*4 each (+ the gathers S[src], H[rev] replace A:
 // 3 rows per edge), partial writes ksplit*h*h*4; flops 2*E*h^2.
@@ -25,6 +43,7 @@
 
 namespace nt {
 int cu_count();   // csrc/tile_plan.hip: the current device's CU count, queried once per device
+int xcd_count();  // csrc/tile_plan.hip: the current device's XCD count, queried once per device
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1347,38 +1366,45 @@ int reduce_partials(const float* part, const float* part_db, int64_t h, int kspl
   return NT_OK;
 }
 
-struct Plan {
-  int tiles, ksplit, chunk_steps;
+// ---------------------------------------------------------------------------------------------
+// Host side: one route table, one split-K plan, one launch path.
+
+enum RouteId { kTiled, kX6Wide, kFk, kFkWide, kBf16, kBf16Wide, kNumRoutes };
+
+struct Route {
+  int icols, jcols;   // G columns (dW rows) and A columns of a workgroup; icols 0: all of G's columns
+  int min_h;          // the route runs above this h only
+  int slots_per_cu;   // resident workgroups per CU that one round of the grid may fill
+  int round_to;       // ksplit is a multiple of this (and at least this) while the edges allow
+  int threads, lds;   // block shape and dynamic LDS bytes
+  bool lds_attr;      // raise the kernel's dynamic-LDS limit first (the x6 wide kernel never has)
 };
 
-Plan make_plan(int64_t E, int64_t h) {
-  Plan p;
-  const int tpr = (int)((h + kT - 1) / kT);
-  p.tiles = tpr * tpr;
-  const int64_t steps = (E + kK - 1) / kK;
-  // one round of workgroups: ksplit = the largest multiple of 8 with tiles * ksplit <= resident slots
-  const int slots = kWgPerCu * (cu_count() > 0 ? cu_count() : 256);
-  int64_t ks = slots / p.tiles / 8 * 8;
-  if (ks < 8) ks = 8;
-  if (ks > steps) ks = steps > 0 ? steps : 1;
-  p.chunk_steps = (int)((steps + ks - 1) / ks);
-  if (p.chunk_steps < 1) p.chunk_steps = 1;
-  p.ksplit = (int)((steps + p.chunk_steps - 1) / p.chunk_steps);
-  if (p.ksplit < 1) p.ksplit = 1;
-  return p;
-}
+constexpr Route kRoutes[kNumRoutes] = {
+    /* kTiled    */ {kT, kT, 0, kWgPerCu, 8, 256, kBufs * 2 * kSlabB, false},
+    /* kX6Wide   */ {0, kWJ, 0, 1, 1, 512, kWLds, false},
+    /* kFk       */ {0, kFJ, 0, 1, 1, 512, kFLds, true},
+    /* kFkWide   */ {kYI, kYJ, kWI, 1, 1, 512, kYLds, true},
+    /* kBf16     */ {0, kWJ, 0, 1, 1, 512, kBLds, true},
+    /* kBf16Wide */ {kXI, kXJ, kBI, 1, 1, 512, kXLds, true},
+};
 
-struct WPlan {
+int iblocks_of(const Route& r, int64_t h) { return r.icols ? (int)((h + r.icols - 1) / r.icols) : 1; }
+int jblocks_of(const Route& r, int64_t h) { return (int)((h + r.jcols - 1) / r.jcols); }
+
+struct Plan {
   int ksplit, chunk_steps;
 };
 
-// one workgroup per CU: ksplit = CUs / jblocks chunks of the edge range (jcols: A columns per block)
-WPlan make_wide_plan(int64_t E, int64_t h, int jcols = kWJ) {
-  WPlan p;
-  const int jblocks = (int)((h + jcols - 1) / jcols);
+// One round of workgroups: ksplit = the largest multiple of round_to with tiles * ksplit <= the
+// resident slots (at least round_to), clamped to the number of 32-edge steps; the chunks are then
+// evened out, so ksplit * chunk_steps covers the steps with no empty chunk.
+Plan split_k_plan(int64_t E, int64_t tiles, int slots_per_cu, int round_to) {
+  Plan p;
   const int64_t steps = (E + kK - 1) / kK;
-  int64_t ks = (cu_count() > 0 ? cu_count() : 256) / jblocks;
-  if (ks < 1) ks = 1;
+  const int64_t slots = (int64_t)slots_per_cu * (cu_count() > 0 ? cu_count() : 256);
+  int64_t ks = slots / tiles / round_to * round_to;
+  if (ks < round_to) ks = round_to;
   if (ks > steps) ks = steps > 0 ? steps : 1;
   p.chunk_steps = (int)((steps + ks - 1) / ks);
   if (p.chunk_steps < 1) p.chunk_steps = 1;
@@ -1387,52 +1413,130 @@ WPlan make_wide_plan(int64_t E, int64_t h, int jcols = kWJ) {
   return p;
 }
 
-// the bf16 wide kernel: one workgroup per CU, ksplit = CUs / (i-blocks x j-blocks) chunks (at least
-// one; from h = 4096 the tiles alone fill the machine).  Never more chunks than make_wide_plan's.
-WPlan make_bf16_wide_plan(int64_t E, int64_t h) {
-  WPlan p;
-  const int64_t tiles = ((h + kXI - 1) / kXI) * ((h + kXJ - 1) / kXJ);
-  const int64_t steps = (E + kK - 1) / kK;
-  int64_t ks = (cu_count() > 0 ? cu_count() : 256) / tiles;
-  if (ks < 1) ks = 1;
-  if (ks > steps) ks = steps > 0 ? steps : 1;
-  p.chunk_steps = (int)((steps + ks - 1) / ks);
-  if (p.chunk_steps < 1) p.chunk_steps = 1;
-  p.ksplit = (int)((steps + p.chunk_steps - 1) / p.chunk_steps);
-  if (p.ksplit < 1) p.ksplit = 1;
-  return p;
+Plan plan_of(const Route& r, int64_t E, int64_t h) {
+  return split_k_plan(E, (int64_t)iblocks_of(r, h) * jblocks_of(r, h), r.slots_per_cu, r.round_to);
 }
 
-// the fp32 wide kernel: one workgroup per CU, ksplit = CUs / (i-blocks x j-blocks) chunks (at least one).
-// Its blocks are at least 128 columns wide, so never more chunks than make_wide_plan(E, h, kFJ)'s.
-WPlan make_fk_wide_plan(int64_t E, int64_t h) {
-  WPlan p;
-  const int64_t tiles = ((h + kYI - 1) / kYI) * ((h + kYJ - 1) / kYJ);
-  const int64_t steps = (E + kK - 1) / kK;
-  int64_t ks = (cu_count() > 0 ? cu_count() : 256) / tiles;
-  if (ks < 1) ks = 1;
-  if (ks > steps) ks = steps > 0 ? steps : 1;
-  p.chunk_steps = (int)((steps + ks - 1) / ks);
-  if (p.chunk_steps < 1) p.chunk_steps = 1;
-  p.ksplit = (int)((steps + p.chunk_steps - 1) / p.chunk_steps);
-  if (p.ksplit < 1) p.ksplit = 1;
-  return p;
+// What an entry was called with.  fn is the entry's name: the helpers below report errors under it.
+struct Call {
+  const char* fn;
+  const void* G;
+  const void* H;
+  const void* S;
+  const int64_t* src;
+  const int64_t* rev;
+  const float* amax_G;
+  const float* amax_HS;
+  int64_t V, E, h;
+  int act;
+  float alpha;
+  void* workspace;
+  void* dW_out;
+  void* db_out;
+  hipStream_t stream;
+};
+
+// NT_REQUIRE and NT_HIP for code the entries share, where __func__ is not the entry's name
+#define WG_REQUIRE(cond, code, msg)                      \
+  do {                                                   \
+    if (!(cond)) {                                       \
+      set_error(std::string(c.fn) + ": " + (msg));       \
+      return (code);                                     \
+    }                                                    \
+  } while (0)
+#define WG_HIP(expr)                                                             \
+  do {                                                                           \
+    hipError_t _e = (expr);                                                      \
+    if (_e != hipSuccess) {                                                      \
+      set_error(std::string(c.fn) + ": " #expr " -> " + hipGetErrorString(_e)); \
+      return NT_EHIP;                                                            \
+    }                                                                            \
+  } while (0)
+
+// The checks both entries make after their dtype check, in the order callers have come to know.  An
+// entry passes in the outcome of the two rules only it has: its size rule (with the rule's text) and
+// whether src and rev are paired as it needs.  NT_OK with *done false: go on to the launch; otherwise
+// the entry returns the status (E == 0 is done here: zero gradients, no launch).
+int entry_front(const Call& c, bool size_rule_ok, const char* size_rule, bool src_rev_paired, bool* done) {
+  *done = true;
+  WG_REQUIRE(c.act >= NT_ACT_IDENTITY && c.act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
+  WG_REQUIRE(c.V >= 0 && c.E >= 0 && c.h > 0, NT_EINVAL, "bad sizes");
+  WG_REQUIRE(size_rule_ok, NT_EUNSUPPORTED, size_rule);
+  // row indices are narrowed to int for the lane broadcasts
+  WG_REQUIRE(c.V < ((int64_t)1 << 31) && c.E < ((int64_t)1 << 31), NT_EUNSUPPORTED,
+             std::string(c.fn) + ": V and E must be < 2^31");
+  WG_REQUIRE(src_rev_paired, NT_EINVAL, "src and rev: both or neither");
+  WG_REQUIRE(c.dW_out, NT_EINVAL, "NULL dW_out");
+  if (c.E == 0) {
+    WG_HIP(hipMemsetAsync(c.dW_out, 0, c.h * c.h * sizeof(float), c.stream));
+    if (c.db_out) WG_HIP(hipMemsetAsync(c.db_out, 0, c.h * sizeof(float), c.stream));
+    return NT_OK;
+  }
+  *done = false;
+  return NT_OK;
 }
+
+// The fields in which the six argument blocks differ.  The blocks stay apart because the kernels'
+// generated code follows the block's layout: with one merged block wgrad_bf16_wide_kernel ran 23 % and
+// wgrad_fk_kernel 1 % slower (profiles/wgrad_refactor/timing.txt).
+void set_blocks(WgArgs& a, int ib, int jb) { a.tiles = ib * jb; }
+void set_blocks(WwArgs& a, int, int jb) { a.jblocks = jb; }
+void set_blocks(WfArgs& a, int, int jb) { a.jblocks = jb; }
+void set_blocks(WbArgs& a, int, int jb) { a.jblocks = jb; }
+void set_blocks(WxArgs& a, int ib, int jb) { a.iblocks = ib, a.jblocks = jb; }
+void set_blocks(WyArgs& a, int ib, int jb) { a.iblocks = ib, a.jblocks = jb; }
+template <typename A>
+void set_amax(A&, const Call&) {}
+void set_amax(WfArgs& a, const Call& c) { a.amax_G = c.amax_G, a.amax_HS = c.amax_HS; }
+void set_amax(WyArgs& a, const Call& c) { a.amax_G = c.amax_G, a.amax_HS = c.amax_HS; }
+
+// Fill the argument block, pick the activation's instance, launch one route and reduce its partials.
+template <typename A>
+int launch(RouteId id, const Call& c, void (*k_identity)(A), void (*k_relu)(A), void (*k_generic)(A)) {
+  const Route& r = kRoutes[id];
+  const Plan p = plan_of(r, c.E, c.h);
+  const int tiles = iblocks_of(r, c.h) * jblocks_of(r, c.h);
+  A a;
+  a.G = (decltype(a.G))c.G;
+  a.H = (decltype(a.H))c.H;
+  a.S = (decltype(a.S))c.S;
+  a.src = c.src;
+  a.rev = c.rev;
+  set_amax(a, c);
+  a.E = c.E;
+  a.h = c.h;
+  set_blocks(a, iblocks_of(r, c.h), jblocks_of(r, c.h));
+  a.ksplit = p.ksplit;
+  a.chunk_steps = p.chunk_steps;
+  a.xcds = xcd_count();
+  a.alpha = c.alpha;
+  a.act = c.act;
+  a.part = (float*)c.workspace;
+  a.part_db = c.db_out ? a.part + (int64_t)p.ksplit * c.h * c.h : nullptr;
+  auto kern = c.act == NT_ACT_IDENTITY ? k_identity : c.act == NT_ACT_RELU ? k_relu : k_generic;
+  if (r.lds_attr) WG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, r.lds));
+  kern<<<tiles * p.ksplit, r.threads, r.lds, c.stream>>>(a);
+  WG_HIP(hipGetLastError());
+  return reduce_partials(a.part, a.part_db, c.h, p.ksplit, (float*)c.dW_out, (float*)c.db_out, c.stream);
+}
+
+#undef WG_REQUIRE
+#undef WG_HIP
+
+// the three instances launch() chooses from
+#define WG_ACT_INSTANCES(kernel) kernel<NT_ACT_IDENTITY>, kernel<NT_ACT_RELU>, kernel<-1>
 
 }  // namespace
-
-int xcd_count();  // csrc/tile_plan.hip: the current device's XCD count, queried once per device
 }  // namespace nt
 
+// The partials of every route that takes this h fit (a route's upper h bound is not applied, so the
+// value only grows with h and stays what callers have recorded)
 extern "C" int64_t nt_dmpnn_weight_grad_workspace(int64_t E, int64_t h) {
   if (E < 0 || h <= 0) return -1;
-  const nt::Plan p = nt::make_plan(E, h);
-  const nt::WPlan q = nt::make_wide_plan(E, h), f = nt::make_wide_plan(E, h, nt::kFJ);
-  int64_t ks = p.ksplit > q.ksplit ? p.ksplit : q.ksplit;  // every kernel fits
-  ks = ks > f.ksplit ? ks : f.ksplit;
-  if (h > nt::kBI) {  // the bf16 wide kernel's plan (never above the others: see make_bf16_wide_plan)
-    const nt::WPlan x = nt::make_bf16_wide_plan(E, h);
-    ks = ks > x.ksplit ? ks : x.ksplit;
+  int64_t ks = 0;
+  for (const nt::Route& r : nt::kRoutes) {
+    const int k = h > r.min_h ? nt::plan_of(r, E, h).ksplit : 0;
+    ks = ks > k ? ks : k;
   }
   return ks * (h * h + h) * (int64_t)sizeof(float);
 }
@@ -1444,140 +1548,31 @@ extern "C" int nt_dmpnn_weight_grad(const void* G, const void* H, const void* S,
   using namespace nt;
   clear_error();
   NT_REQUIRE(dtype == NT_F32 || dtype == NT_BF16, NT_EUNSUPPORTED, "nt_dmpnn_weight_grad: fp32 or bf16");
-  NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
-  NT_REQUIRE(V >= 0 && E >= 0 && h > 0, NT_EINVAL, "bad sizes");
-  NT_REQUIRE(dtype == NT_F32 || (((h <= kBI && h % 2 == 0) || (h % 8 == 0 && h <= kXMaxH)) && src && rev),
-             NT_EUNSUPPORTED,
-             "nt_dmpnn_weight_grad: bf16 needs src and rev, and an even h <= 512 or h % 8 == 0 and h <= 8192");
-  // row indices are narrowed to int for the lane broadcasts
-  NT_REQUIRE(V < ((int64_t)1 << 31) && E < ((int64_t)1 << 31), NT_EUNSUPPORTED,
-             "nt_dmpnn_weight_grad: V and E must be < 2^31");
-  NT_REQUIRE((src == nullptr) == (rev == nullptr), NT_EINVAL, "src and rev: both or neither");
-  NT_REQUIRE(dW_out, NT_EINVAL, "NULL dW_out");
-  hipStream_t stream = as_stream(stream_);
-  if (E == 0) {
-    NT_HIP(hipMemsetAsync(dW_out, 0, h * h * sizeof(float), stream));
-    if (db_out) NT_HIP(hipMemsetAsync(db_out, 0, h * sizeof(float), stream));
-    return NT_OK;
-  }
+  const Call c{__func__, G, H, S, src, rev, nullptr, nullptr, V, E, h, act, act_alpha,
+               workspace, dW_out, db_out, as_stream(stream_)};
+  const bool size_rule_ok =
+      dtype == NT_F32 || (((h <= kBI && h % 2 == 0) || (h % 8 == 0 && h <= kXMaxH)) && src && rev);
+  bool done;
+  const int rc = entry_front(
+      c, size_rule_ok,
+      "nt_dmpnn_weight_grad: bf16 needs src and rev, and an even h <= 512 or h % 8 == 0 and h <= 8192",
+      (src == nullptr) == (rev == nullptr), &done);
+  if (done) return rc;
   NT_REQUIRE(G && S && (src == nullptr || H), NT_EINVAL, "NULL pointer");
-  const Plan p = make_plan(E, h);
   NT_REQUIRE(workspace && workspace_bytes >= nt_dmpnn_weight_grad_workspace(E, h), NT_EINVAL,
              "workspace too small (nt_dmpnn_weight_grad_workspace)");
-  WgArgs a;
-  a.G = (const float*)G;
-  a.H = (const float*)H;
-  a.S = (const float*)S;
-  a.src = src;
-  a.rev = rev;
-  a.E = E;
-  a.h = h;
-  a.tiles = p.tiles;
-  a.ksplit = p.ksplit;
-  a.chunk_steps = p.chunk_steps;
-  a.xcds = xcd_count();
-  a.alpha = act_alpha;
-  a.act = act;
-  a.part = (float*)workspace;
-  a.part_db = db_out ? a.part + (int64_t)p.ksplit * h * h : nullptr;
-  if (dtype == NT_BF16 && h > kBI) {  // dW tiled in both dimensions
+  if (dtype == NT_BF16 && h > kBI) {
     NT_REQUIRE(((uintptr_t)G | (uintptr_t)H | (uintptr_t)S) % 16 == 0, NT_EINVAL,
                "nt_dmpnn_weight_grad: bf16 h > 512 needs 16-byte aligned G, H and S");
-    const WPlan q = make_bf16_wide_plan(E, h);
-    WxArgs b;
-    b.G = (const uint16_t*)G;
-    b.H = (const uint16_t*)H;
-    b.S = (const uint16_t*)S;
-    b.src = src;
-    b.rev = rev;
-    b.E = E;
-    b.h = h;
-    b.iblocks = (int)((h + kXI - 1) / kXI);
-    b.jblocks = (int)((h + kXJ - 1) / kXJ);
-    b.ksplit = q.ksplit;
-    b.chunk_steps = q.chunk_steps;
-    b.xcds = xcd_count();
-    b.alpha = act_alpha;
-    b.act = act;
-    b.part = (float*)workspace;
-    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
-    const int grid = b.iblocks * b.jblocks * q.ksplit;
-    auto kern = act == NT_ACT_IDENTITY ? wgrad_bf16_wide_kernel<NT_ACT_IDENTITY>
-                : act == NT_ACT_RELU   ? wgrad_bf16_wide_kernel<NT_ACT_RELU>
-                                       : wgrad_bf16_wide_kernel<-1>;
-    NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kXLds));
-    kern<<<grid, 512, kXLds, stream>>>(b);
-    NT_LAUNCH_CHECK();
-    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
+    return launch(kBf16Wide, c, WG_ACT_INSTANCES(wgrad_bf16_wide_kernel));
   }
-  if (dtype == NT_BF16) {
-    const WPlan q = make_wide_plan(E, h);
-    WbArgs b;
-    b.G = (const uint16_t*)G;
-    b.H = (const uint16_t*)H;
-    b.S = (const uint16_t*)S;
-    b.src = src;
-    b.rev = rev;
-    b.E = E;
-    b.h = h;
-    b.jblocks = (int)((h + kWJ - 1) / kWJ);
-    b.ksplit = q.ksplit;
-    b.chunk_steps = q.chunk_steps;
-    b.xcds = xcd_count();
-    b.alpha = act_alpha;
-    b.act = act;
-    b.part = (float*)workspace;
-    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
-    const int grid = b.jblocks * q.ksplit;
-    auto kern = act == NT_ACT_IDENTITY ? wgrad_bf16_kernel<NT_ACT_IDENTITY>
-                : act == NT_ACT_RELU   ? wgrad_bf16_kernel<NT_ACT_RELU>
-                                       : wgrad_bf16_kernel<-1>;
-    NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kBLds));
-    kern<<<grid, 512, kBLds, stream>>>(b);
-    NT_LAUNCH_CHECK();
-    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
-  }
-  if (src && h <= kWI) {  // the wide kernel: 128-column blocks of A against all of G
-    const int jblocks = (int)((h + kWJ - 1) / kWJ);
-    const WPlan q = make_wide_plan(E, h);
-    WwArgs b;
-    b.G = (const float*)G;
-    b.H = (const float*)H;
-    b.S = (const float*)S;
-    b.src = src;
-    b.rev = rev;
-    b.E = E;
-    b.h = h;
-    b.jblocks = jblocks;
-    b.ksplit = q.ksplit;
-    b.chunk_steps = q.chunk_steps;
-    b.xcds = xcd_count();
-    b.alpha = act_alpha;
-    b.act = act;
-    b.part = (float*)workspace;
-    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
-    const int grid = jblocks * q.ksplit;
-    if (act == NT_ACT_IDENTITY)
-      wgrad_wide_kernel<NT_ACT_IDENTITY><<<grid, 512, kWLds, stream>>>(b);
-    else if (act == NT_ACT_RELU)
-      wgrad_wide_kernel<NT_ACT_RELU><<<grid, 512, kWLds, stream>>>(b);
-    else
-      wgrad_wide_kernel<-1><<<grid, 512, kWLds, stream>>>(b);
-    NT_LAUNCH_CHECK();
-    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
-  }
-  const int grid = p.tiles * p.ksplit;
-  const size_t lds = kBufs * 2 * kSlabB;
-  if (!src)
-    wgrad_kernel<NT_ACT_IDENTITY, false><<<grid, 256, lds, stream>>>(a);
-  else if (act == NT_ACT_IDENTITY)
-    wgrad_kernel<NT_ACT_IDENTITY, true><<<grid, 256, lds, stream>>>(a);
-  else if (act == NT_ACT_RELU)
-    wgrad_kernel<NT_ACT_RELU, true><<<grid, 256, lds, stream>>>(a);
-  else
-    wgrad_kernel<-1, true><<<grid, 256, lds, stream>>>(a);
-  NT_LAUNCH_CHECK();
-  return reduce_partials(a.part, a.part_db, h, p.ksplit, (float*)dW_out, (float*)db_out, stream);
+  if (dtype == NT_BF16) return launch(kBf16, c, WG_ACT_INSTANCES(wgrad_bf16_kernel));
+  if (src && h <= kWI) return launch(kX6Wide, c, WG_ACT_INSTANCES(wgrad_wide_kernel));
+  if (src)
+    return launch(kTiled, c, wgrad_kernel<NT_ACT_IDENTITY, true>, wgrad_kernel<NT_ACT_RELU, true>,
+                         wgrad_kernel<-1, true>);
+  const auto dense = wgrad_kernel<NT_ACT_IDENTITY, false>;  // A = S: no message, so no activation
+  return launch(kTiled, c, dense, dense, dense);
 }
 
 extern "C" int nt_dmpnn_weight_grad_fk(const void* G, const void* H, const void* S, const int64_t* src,
@@ -1588,79 +1583,20 @@ extern "C" int nt_dmpnn_weight_grad_fk(const void* G, const void* H, const void*
   using namespace nt;
   clear_error();
   NT_REQUIRE(dtype == NT_F32, NT_EUNSUPPORTED, "nt_dmpnn_weight_grad_fk: fp32 only");
-  NT_REQUIRE(act >= NT_ACT_IDENTITY && act <= NT_ACT_SIGMOID, NT_EINVAL, "bad act code");
-  NT_REQUIRE(V >= 0 && E >= 0 && h > 0, NT_EINVAL, "bad sizes");
-  NT_REQUIRE(h <= kWI || (h % 4 == 0 && h <= kYMaxH), NT_EUNSUPPORTED,
-             "nt_dmpnn_weight_grad_fk: h <= 320, or h % 4 == 0 and h <= 8192 (else nt_dmpnn_weight_grad)");
-  NT_REQUIRE(V < ((int64_t)1 << 31) && E < ((int64_t)1 << 31), NT_EUNSUPPORTED,
-             "nt_dmpnn_weight_grad_fk: V and E must be < 2^31");
-  NT_REQUIRE(dW_out, NT_EINVAL, "NULL dW_out");
-  hipStream_t stream = as_stream(stream_);
-  if (E == 0) {
-    NT_HIP(hipMemsetAsync(dW_out, 0, h * h * sizeof(float), stream));
-    if (db_out) NT_HIP(hipMemsetAsync(db_out, 0, h * sizeof(float), stream));
-    return NT_OK;
-  }
+  const Call c{__func__, G, H, S, src, rev, amax_G, amax_HS, V, E, h, act, act_alpha,
+               workspace, dW_out, db_out, as_stream(stream_)};
+  bool done;
+  const int rc = entry_front(
+      c, h <= kWI || (h % 4 == 0 && h <= kYMaxH),
+      "nt_dmpnn_weight_grad_fk: h <= 320, or h % 4 == 0 and h <= 8192 (else nt_dmpnn_weight_grad)", true, &done);
+  if (done) return rc;
   NT_REQUIRE(G && S && H && src && rev && amax_G && amax_HS, NT_EINVAL, "NULL pointer");
   NT_REQUIRE(workspace && workspace_bytes >= nt_dmpnn_weight_grad_workspace(E, h), NT_EINVAL,
              "workspace too small (nt_dmpnn_weight_grad_workspace)");
-  if (h > kWI) {  // dW tiled in both dimensions
+  if (h > kWI) {
     NT_REQUIRE(((uintptr_t)G | (uintptr_t)H | (uintptr_t)S) % 16 == 0, NT_EINVAL,
                "nt_dmpnn_weight_grad_fk: h > 320 needs 16-byte aligned G, H and S");
-    const WPlan q = make_fk_wide_plan(E, h);
-    WyArgs b;
-    b.G = (const float*)G;
-    b.H = (const float*)H;
-    b.S = (const float*)S;
-    b.src = src;
-    b.rev = rev;
-    b.amax_G = amax_G;
-    b.amax_HS = amax_HS;
-    b.E = E;
-    b.h = h;
-    b.iblocks = (int)((h + kYI - 1) / kYI);
-    b.jblocks = (int)((h + kYJ - 1) / kYJ);
-    b.ksplit = q.ksplit;
-    b.chunk_steps = q.chunk_steps;
-    b.xcds = xcd_count();
-    b.alpha = act_alpha;
-    b.act = act;
-    b.part = (float*)workspace;
-    b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
-    const int grid = b.iblocks * b.jblocks * q.ksplit;
-    auto kern = act == NT_ACT_IDENTITY ? wgrad_fk_wide_kernel<NT_ACT_IDENTITY>
-                : act == NT_ACT_RELU   ? wgrad_fk_wide_kernel<NT_ACT_RELU>
-                                       : wgrad_fk_wide_kernel<-1>;
-    NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kYLds));
-    kern<<<grid, 512, kYLds, stream>>>(b);
-    NT_LAUNCH_CHECK();
-    return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
+    return launch(kFkWide, c, WG_ACT_INSTANCES(wgrad_fk_wide_kernel));
   }
-  const WPlan q = make_wide_plan(E, h, kFJ);
-  WfArgs b;
-  b.G = (const float*)G;
-  b.H = (const float*)H;
-  b.S = (const float*)S;
-  b.src = src;
-  b.rev = rev;
-  b.amax_G = amax_G;
-  b.amax_HS = amax_HS;
-  b.E = E;
-  b.h = h;
-  b.jblocks = (int)((h + kFJ - 1) / kFJ);
-  b.ksplit = q.ksplit;
-  b.chunk_steps = q.chunk_steps;
-  b.xcds = xcd_count();
-  b.alpha = act_alpha;
-  b.act = act;
-  b.part = (float*)workspace;
-  b.part_db = db_out ? b.part + (int64_t)q.ksplit * h * h : nullptr;
-  const int grid = b.jblocks * q.ksplit;
-  auto kern = act == NT_ACT_IDENTITY ? wgrad_fk_kernel<NT_ACT_IDENTITY>
-              : act == NT_ACT_RELU   ? wgrad_fk_kernel<NT_ACT_RELU>
-                                     : wgrad_fk_kernel<-1>;
-  NT_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kFLds));
-  kern<<<grid, 512, kFLds, stream>>>(b);
-  NT_LAUNCH_CHECK();
-  return reduce_partials(b.part, b.part_db, h, q.ksplit, (float*)dW_out, (float*)db_out, stream);
+  return launch(kFk, c, WG_ACT_INSTANCES(wgrad_fk_kernel));
 }
